@@ -25,11 +25,17 @@ cross-host-shaped socket lane), ``fedavg`` (config 4: Llama-3-8B
 gradients, intra-party RCCL + cross-party exchange + HIP combine;
 ``RAYFED_BENCH_ARENA=1`` for the zero-pack shared-gradient arena).
 
-The default tiny N=1 GPU run ALSO measures push / fedavg / arena-fedavg /
-socket-push / tls-push in subprocesses and reports them under ``config.extras`` so a
-single driver invocation observes every data-plane headline
-(``RAYFED_BENCH_EXTRAS=0`` skips).  The JSON line always carries
-``transport`` (cpp/asyncio/grpc) and, for data modes, the ``lane``.
+A plain run does only what its headline figure needs: set up, warm up,
+time ``--steps`` steps, print the JSON line.  ``--full`` (tiny N=1 GPU run)
+ALSO measures push / fedavg / arena-fedavg / socket-push / tls-push in
+subprocesses and reports them under ``config.extras`` so a single
+invocation observes every data-plane headline.  The JSON line always
+carries ``transport`` (cpp/asyncio/grpc) and, for data modes, the ``lane``.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its
+caller (the ``fed.get`` value of that step) as ``DIR/last_step_result.npy``
+(float64).  Inputs are seeded, so two builds run with the same arguments
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -117,9 +123,19 @@ def _warm_transport(addresses, party, rounds: int = 32):
                 time.sleep(0.05)
 
 
+def _dump_outputs(dump_dir: str, result) -> None:
+    """--dump-outputs: the value the last timed step handed its caller."""
+    import numpy as np
+
+    os.makedirs(dump_dir, exist_ok=True)
+    arr = np.atleast_1d(np.asarray(result, dtype=np.float64))
+    np.save(os.path.join(dump_dir, "last_step_result.npy"), arr)
+
+
 # ------------------------------------------------------------------ tiny mode
 def _tiny_driver(party: str, addresses, steps: int, warmup: int, device: int,
-                 job_name: str, tls_config=None, barrier_cb=None, result_q=None):
+                 job_name: str, tls_config=None, barrier_cb=None, result_q=None,
+                 dump_dir=None):
     """The many_tiny_tasks loop; identical code runs in every party."""
     import rayfed_amd as fed
 
@@ -173,14 +189,15 @@ def _tiny_driver(party: str, addresses, steps: int, warmup: int, device: int,
         barrier_cb()
     debug = os.environ.get("RAYFED_BENCH_DEBUG") == "1"
     stamps = [0.0] * (steps + 1) if debug else None
+    last = None
     t0 = time.perf_counter()
     if debug:
         for i in range(steps):
-            one_iter()
+            last = one_iter()
             stamps[i + 1] = time.perf_counter() - t0
     else:
         for _ in range(steps):
-            one_iter()
+            last = one_iter()
     if use_gpu:
         import torch
 
@@ -188,6 +205,8 @@ def _tiny_driver(party: str, addresses, steps: int, warmup: int, device: int,
     elapsed = time.perf_counter() - t0
     if barrier_cb is not None:
         barrier_cb()
+    if dump_dir is not None:
+        _dump_outputs(dump_dir, last)
     if debug and party == sorted(addresses)[0]:
         per = [
             round((stamps[i + 1] - stamps[i]) * 1e6)
@@ -227,7 +246,7 @@ def _detect_lane(nbytes: int, dtype, device_type: str) -> str:
 
 def _push_driver(party: str, addresses, steps: int, warmup: int, device: int,
                  job_name: str, nbytes: int, tls_config=None, barrier_cb=None,
-                 result_q=None):
+                 result_q=None, dump_dir=None):
     """BASELINE config 3: bf16 tensor push alice→bob; end-to-end GB/s."""
     import torch
 
@@ -248,6 +267,7 @@ def _push_driver(party: str, addresses, steps: int, warmup: int, device: int,
     @fed.remote
     class Producer:
         def __init__(self, dev, numel):
+            torch.manual_seed(0)  # same payload run to run
             self._t = torch.randn(numel, dtype=torch.bfloat16, device=dev)
 
         def produce(self):
@@ -274,14 +294,17 @@ def _push_driver(party: str, addresses, steps: int, warmup: int, device: int,
         torch.cuda.synchronize()
     if barrier_cb is not None:
         barrier_cb()
+    last = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        one_iter()
+        last = one_iter()
     if use_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if barrier_cb is not None:
         barrier_cb()
+    if dump_dir is not None:
+        _dump_outputs(dump_dir, last)
     lane = "n/a"
     if party == "alice":
         try:
@@ -317,7 +340,7 @@ def llama3_8b_grad_shapes(layers: int = 32, vocab: int = 128256):
 
 def _fedavg_driver(party, addresses, steps, warmup, device, job_name, layers,
                    vocab=128256, party_group=None, barrier_cb=None,
-                   result_q=None):
+                   result_q=None, dump_dir=None):
     """Party-leader FedAvg round: (optional) intra-party RCCL all-reduce,
     cross-party gradient exchange through the fed data plane, HIP weighted
     combine (csrc fedavg_reduce_)."""
@@ -424,14 +447,17 @@ def _fedavg_driver(party, addresses, steps, warmup, device, job_name, layers,
         torch.cuda.synchronize()
     if barrier_cb is not None:
         barrier_cb()
+    last = None
     t0 = time.perf_counter()
     for i in range(steps):
-        round_once(("s", i))
+        last = round_once(("s", i))
     if use_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if barrier_cb is not None:
         barrier_cb()
+    if dump_dir is not None:
+        _dump_outputs(dump_dir, last)
     try:
         lane = _detect_lane(nbytes, dtype, "cuda" if use_gpu else "cpu")
     except Exception:  # noqa: BLE001
@@ -445,7 +471,8 @@ def _fedavg_driver(party, addresses, steps, warmup, device, job_name, layers,
 _DRIVERS = {"tiny": _tiny_driver, "push": _push_driver, "fedavg": _fedavg_driver}
 
 
-def _run_fedavg_torchrun(steps, warmup, layers, vocab, rank, world, local_rank):
+def _run_fedavg_torchrun(steps, warmup, layers, vocab, rank, world, local_rank,
+                         dump_dir=None):
     """Leaders (ranks 0, W/2) run the fed exchange; every rank joins its
     party's RCCL group for the intra-party gradient all-reduce."""
     import torch
@@ -480,7 +507,7 @@ def _run_fedavg_torchrun(steps, warmup, layers, vocab, rank, world, local_rank):
         elapsed, nbytes, transport, lane = _fedavg_driver(
             party, addresses, steps, warmup, local_rank, "bench_fedavg", layers,
             vocab=vocab, party_group=group if half > 1 else None,
-            barrier_cb=barrier,
+            barrier_cb=barrier, dump_dir=dump_dir if rank == 0 else None,
         )
     else:
         # Member rank: mirror the leader's per-round intra-party all-reduce.
@@ -510,7 +537,8 @@ def _run_fedavg_torchrun(steps, warmup, layers, vocab, rank, world, local_rank):
     return float(t.item()), nbytes, transport, lane
 
 
-def _run_single_process(mode, steps, warmup, extra=None, parties=2, tls=False):
+def _run_single_process(mode, steps, warmup, extra=None, parties=2, tls=False,
+                        dump_dir=None):
     """N=1: first party in-process, the rest forked, all on GPU 0."""
     _pin_cpus(0, 1)  # forked parties inherit the affinity set
     from tests._util import make_addresses  # free-port helper
@@ -544,7 +572,8 @@ def _run_single_process(mode, steps, warmup, extra=None, parties=2, tls=False):
     for p in procs:
         p.start()
     elapsed = _DRIVERS[mode](
-        names[0], addresses, steps, warmup, 0, f"bench_{mode}", *args_extra
+        names[0], addresses, steps, warmup, 0, f"bench_{mode}", *args_extra,
+        dump_dir=dump_dir,
     )
     for p in procs:
         p.join(timeout=600)
@@ -554,7 +583,8 @@ def _run_single_process(mode, steps, warmup, extra=None, parties=2, tls=False):
     return elapsed
 
 
-def _run_torchrun(mode, steps, warmup, push_bytes, rank, world, local_rank):
+def _run_torchrun(mode, steps, warmup, push_bytes, rank, world, local_rank,
+                  dump_dir=None):
     import torch.distributed as dist
 
     _pin_cpus(local_rank, world)
@@ -580,6 +610,7 @@ def _run_torchrun(mode, steps, warmup, push_bytes, rank, world, local_rank):
     out = _DRIVERS[mode](
         party, addresses, steps, warmup, local_rank, f"bench_{mode}_lane{lane}",
         *args_extra, barrier_cb=barrier,
+        dump_dir=dump_dir if rank == 0 else None,
     )
     if mode == "push":
         elapsed, transport, data_lane = out
@@ -596,10 +627,9 @@ def _run_torchrun(mode, steps, warmup, push_bytes, rank, world, local_rank):
 
 
 def _run_extras() -> dict:
-    """Measure BASELINE configs 3 (4 GiB push) and 4 (FedAvg) in fresh
-    subprocesses so the driver's default run observes the data-plane
-    numbers too.  Failures degrade to an error note, never crash the
-    headline run."""
+    """--full: measure BASELINE configs 3 (4 GiB push) and 4 (FedAvg) in
+    fresh subprocesses so one run observes the data-plane numbers too.
+    Failures degrade to an error note, never crash the headline run."""
     import subprocess
 
     out = {}
@@ -624,7 +654,6 @@ def _run_extras() -> dict:
           "--push-gib", "2", "--tls"], 360, {"RAYFED_SHM": "0"}),
     ]
     env = dict(os.environ)
-    env["RAYFED_BENCH_EXTRAS"] = "0"
     for name, flags, tmo, extra_env in specs:
         try:
             r = subprocess.run(
@@ -650,8 +679,10 @@ def _run_extras() -> dict:
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=2000)
-    p.add_argument("--warmup", type=int, default=200)
+    p.add_argument("--steps", type=int, default=None,
+                   help="timed steps (default: 2000 tiny, 10 push/fedavg)")
+    p.add_argument("--warmup", type=int, default=None,
+                   help="untimed steps (default: 200 tiny, 2 push/fedavg)")
     p.add_argument("--mode", choices=["tiny", "push", "fedavg"], default="tiny")
     p.add_argument("--push-gib", type=float, default=4.0,
                    help="tensor size for --mode push (GiB)")
@@ -663,12 +694,23 @@ def main():
                    help="party count for --mode tiny at N=1 (config 5 uses 3)")
     p.add_argument("--tls", action="store_true",
                    help="self-signed mutual TLS on the cross-silo link")
+    p.add_argument("--full", action="store_true",
+                   help="also measure push / fedavg / socket / TLS lanes in "
+                        "subprocesses (config.extras); tiny N=1 GPU run only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's result to "
+                        "DIR/last_step_result.npy")
     args = p.parse_args()
 
-    if args.mode in ("push", "fedavg") and args.steps > 50:
-        # GiB-scale payload per step: keep the default run under minutes.
-        args.steps = min(args.steps, 10)
-        args.warmup = min(args.warmup, 2)
+    # GiB-scale payload per step in the data modes: their DEFAULT run stays
+    # under minutes.  An explicit --steps / --warmup is always honoured.
+    heavy = args.mode in ("push", "fedavg")
+    if args.steps is None:
+        args.steps = 10 if heavy else 2000
+    if args.warmup is None:
+        args.warmup = 2 if heavy else 200
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
     push_bytes = (int(args.push_gib * (1 << 30)) // 2) * 2  # whole bf16 elements
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -682,13 +724,13 @@ def main():
         if args.mode == "fedavg":
             elapsed, fedavg_nbytes, transport, data_lane = _run_fedavg_torchrun(
                 args.steps, args.warmup, args.layers, args.vocab, rank, world,
-                local_rank,
+                local_rank, dump_dir=args.dump_outputs,
             )
             lanes = 1
         else:
             elapsed, lanes, transport, data_lane = _run_torchrun(
                 args.mode, args.steps, args.warmup, push_bytes, rank, world,
-                local_rank,
+                local_rank, dump_dir=args.dump_outputs,
             )
         if rank != 0:
             return
@@ -698,7 +740,7 @@ def main():
             args.mode, args.steps, args.warmup,
             (args.layers, args.vocab) if args.mode == "fedavg" else push_bytes,
             parties=args.parties if args.mode == "tiny" else 2,
-            tls=args.tls,
+            tls=args.tls, dump_dir=args.dump_outputs,
         )
         if args.mode == "fedavg":
             elapsed, fedavg_nbytes, transport, data_lane = out
@@ -756,15 +798,15 @@ def main():
     if args.mode != "tiny":
         config["lane"] = data_lane
 
-    # Driver-provable data-plane numbers: the default (tiny, N=1, GPU) run
-    # also measures the 4 GiB push and the FedAvg round in subprocesses —
-    # outside the timed region, reported alongside the headline metric.
+    # --full on the (tiny, N=1, GPU) run also measures the 4 GiB push and
+    # the FedAvg round in subprocesses — outside the timed region, reported
+    # alongside the headline metric.
     if (
-        args.mode == "tiny"
+        args.full
+        and args.mode == "tiny"
         and world <= 1
         and not args.tls
         and _has_cuda()
-        and os.environ.get("RAYFED_BENCH_EXTRAS", "1") != "0"
     ):
         config["extras"] = _run_extras()
 

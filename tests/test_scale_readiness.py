@@ -31,7 +31,6 @@ def _torchrun_bench(extra_args, world=8, timeout=420, attempts=2):
     for _ in range(attempts):
         port = free_ports(1)[0]
         env = dict(os.environ)
-        env["RAYFED_BENCH_EXTRAS"] = "0"
         env["RAYFED_BENCH_BASE_PORT"] = str(free_ports(1)[0] + 2000)
         cmd = [
             sys.executable, "-m", "torch.distributed.run",
