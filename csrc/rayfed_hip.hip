@@ -17,6 +17,8 @@
 //     intra-party FedAvg (bf16/f16/f32, fp32 accumulation, vectorized
 //     16-byte loads per lane — CDNA4 guide Appendix B: element-wise ops are
 //     HBM-bound, always vectorize).
+//   * secagg_mask / secagg_aggregate — secure aggregation in Z/2^32 with
+//     in-register ChaCha20 pairwise masks (secagg_kernels.h).
 //
 // Wavefront size is 64 on CDNA4 (not 32); reductions below use width-64
 // shuffles.  Compiled for gfx950 only — no CUDA shims, no multi-arch.
@@ -1218,6 +1220,8 @@ void host_unregister(int64_t ptr) {
   HIP_CHECK(hipHostUnregister(reinterpret_cast<void*>(ptr)));
 }
 
+#include "secagg_kernels.h"
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1250,6 +1254,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fedavg_reduce_mfma_", &fedavg_reduce_mfma_,
         "MFMA (v_mfma_f32_16x16x32_bf16) variant of the weighted combine");
   m.def("masked_add_", &masked_add_, "dst += mask ? src : 0");
+  m.def("secagg_mask_async", &secagg_mask_async,
+        "out_i32 = quantise(x*weight) + sum_k signs[k]*ChaCha20(keys[k]) in "
+        "Z/2^32 (spec + numpy reference: rayfed_amd/ops/secagg_ref.py)");
+  m.def("secagg_aggregate_async", &secagg_aggregate_async,
+        "out = dequantise(ring-sum of int32 inputs - signed ChaCha20 "
+        "corrections of dropped parties)");
   m.def("crc32_combine", &crc32_combine_py, "zlib-style CRC combine");
   m.def("host_register", &host_register, "hipHostRegister an existing mapping");
   m.def("host_unregister", &host_unregister, "hipHostUnregister");

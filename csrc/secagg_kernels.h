@@ -1,0 +1,447 @@
+// Secure aggregation kernels — pairwise ChaCha20 masks in the ring Z/2^32.
+//
+// Included from rayfed_hip.hip inside its anonymous namespace (uses kBlock,
+// kMaxInputs, to_f32/from_f32).  The bit-exact specification and the numpy
+// oracle are in rayfed_amd/ops/secagg_ref.py; tests/test_secagg_gpu.py pins
+// every path here against it.
+//
+//   * secagg_mask_kernel<T>       sender: quantise fp32/bf16/fp16 to
+//     fixed point and add the signed ChaCha20 keystream of up to 15 peers.
+//   * secagg_aggregate_kernel<OutT, EPL>  aggregator: ring-sum of K int32
+//     inputs, subtract the residual keystreams of dropped parties,
+//     dequantise.  EPL = 4 is the pure streaming reduce (no corrections,
+//     one 16-byte load per input per lane, as fedavg_reduce_kernel);
+//     EPL = 16 gives each lane whole ChaCha20 blocks.
+//
+// The keystream lives entirely in registers: one lane runs one 16-word
+// block per peer, keys and signs are kernel arguments (wave-uniform), the
+// rotates compile to single v_alignbit_b32 ops, and there is no LDS.
+#pragma once
+
+#include <type_traits>
+
+constexpr int kSecaggMaxKeys = 16;  // per launch; the wrapper chunks more
+constexpr int kSecaggMaxFracBits = 30;
+constexpr unsigned long long kSecaggMaxElements = 1ull << 36;
+
+struct SecaggKeys {
+  uint32_t key[kSecaggMaxKeys][8];  // little-endian key words
+  int32_t sign[kSecaggMaxKeys];     // +1 / -1
+  int k;
+};
+
+struct SecaggInputs {
+  const int32_t* in[kMaxInputs];
+  int k;
+};
+
+#define SECAGG_QR(a, b, c, d)                           \
+  a += b; d ^= a; d = __builtin_rotateleft32(d, 16);    \
+  c += d; b ^= c; b = __builtin_rotateleft32(b, 12);    \
+  a += b; d ^= a; d = __builtin_rotateleft32(d, 8);     \
+  c += d; b ^= c; b = __builtin_rotateleft32(b, 7);
+
+// One ChaCha20 block (RFC 8439 §2.3 layout): counter `ctr`, nonce words
+// (n0, n1, 0).  `key` is wave-uniform.
+__device__ __forceinline__ void chacha20_block(const uint32_t* key,
+                                               uint32_t ctr, uint32_t n0,
+                                               uint32_t n1, uint32_t out[16]) {
+  const uint32_t c0 = 0x61707865u, c1 = 0x3320646eu, c2 = 0x79622d32u,
+                 c3 = 0x6b206574u;
+  uint32_t x0 = c0, x1 = c1, x2 = c2, x3 = c3;
+  uint32_t x4 = key[0], x5 = key[1], x6 = key[2], x7 = key[3];
+  uint32_t x8 = key[4], x9 = key[5], x10 = key[6], x11 = key[7];
+  uint32_t x12 = ctr, x13 = n0, x14 = n1, x15 = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    SECAGG_QR(x0, x4, x8, x12)
+    SECAGG_QR(x1, x5, x9, x13)
+    SECAGG_QR(x2, x6, x10, x14)
+    SECAGG_QR(x3, x7, x11, x15)
+    SECAGG_QR(x0, x5, x10, x15)
+    SECAGG_QR(x1, x6, x11, x12)
+    SECAGG_QR(x2, x7, x8, x13)
+    SECAGG_QR(x3, x4, x9, x14)
+  }
+  out[0] = x0 + c0;       out[1] = x1 + c1;
+  out[2] = x2 + c2;       out[3] = x3 + c3;
+  out[4] = x4 + key[0];   out[5] = x5 + key[1];
+  out[6] = x6 + key[2];   out[7] = x7 + key[3];
+  out[8] = x8 + key[4];   out[9] = x9 + key[5];
+  out[10] = x10 + key[6]; out[11] = x11 + key[7];
+  out[12] = x12 + ctr;    out[13] = x13 + n0;
+  out[14] = x14 + n1;     out[15] = x15;
+}
+
+#undef SECAGG_QR
+
+// acc[e] += sign * KS(key, round, block ctr)[e] for every key in `keys`.
+// kNegate flips every sign (the aggregator SUBTRACTS its corrections).
+template <bool kNegate>
+__device__ __forceinline__ void secagg_apply_keys(const SecaggKeys& keys,
+                                                  uint32_t ctr, uint32_t n0,
+                                                  uint32_t n1,
+                                                  uint32_t acc[16]) {
+  for (int j = 0; j < keys.k; ++j) {
+    uint32_t ks[16];
+    chacha20_block(keys.key[j], ctr, n0, n1, ks);
+    if ((keys.sign[j] > 0) != kNegate) {  // wave-uniform branch
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] += ks[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] -= ks[e];
+    }
+  }
+}
+
+// sat_i32(rint(fl32(x*w) * scale)); NaN -> 0.  Two separate fp32 multiplies
+// (nothing to contract into an FMA), v_rndne for the half-to-even rint, and
+// an explicit clamp instead of relying on the conversion's saturation.
+__device__ __forceinline__ uint32_t secagg_quantize(float x, float w,
+                                                    float scale) {
+  const float t = x * w;
+  const float r = rintf(t * scale);
+  int q;
+  if (r >= 2147483648.0f) {
+    q = 2147483647;
+  } else if (r <= -2147483648.0f) {
+    q = -2147483647 - 1;
+  } else if (r != r) {
+    q = 0;
+  } else {
+    q = (int)r;
+  }
+  return (uint32_t)q;
+}
+
+// Each lane owns whole 16-element blocks: block b covers elements
+// [16b, 16b+16) of x and uses ChaCha20 counter blk0 + b.  `vec_ok` (both
+// base pointers 16-byte aligned) selects 16-byte loads/stores for full
+// blocks; the ragged final block and misaligned views go element-wise.
+template <typename T>
+__global__ void secagg_mask_kernel(const T* __restrict__ x,
+                                   int32_t* __restrict__ out,
+                                   unsigned long long n,
+                                   unsigned long long blk0, uint32_t n0,
+                                   uint32_t n1, float weight, float scale,
+                                   SecaggKeys keys, bool vec_ok) {
+  const unsigned long long nblk = (n + 15ull) / 16ull;
+  const unsigned long long stride =
+      (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long b =
+           (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+       b < nblk; b += stride) {
+    const unsigned long long base = b * 16ull;
+    const bool vec = vec_ok && (base + 16ull <= n);
+    const int cnt = (base + 16ull <= n) ? 16 : (int)(n - base);
+    uint32_t acc[16];
+    if (vec) {
+      constexpr int kLoads = (int)sizeof(T);  // 16 elements = sizeof(T) uint4
+      uint4 raw[kLoads];
+#pragma unroll
+      for (int v = 0; v < kLoads; ++v)
+        raw[v] = reinterpret_cast<const uint4*>(x + base)[v];
+      const T* e = reinterpret_cast<const T*>(raw);
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        acc[i] = secagg_quantize(to_f32<T>(e[i]), weight, scale);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        acc[i] = (i < cnt)
+                     ? secagg_quantize(to_f32<T>(x[base + i]), weight, scale)
+                     : 0u;
+    }
+    secagg_apply_keys<false>(keys, (uint32_t)(blk0 + b), n0, n1, acc);
+    if (vec) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        reinterpret_cast<uint4*>(out + base)[v] = make_uint4(
+            acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (i < cnt) out[base + i] = (int32_t)acc[i];
+    }
+  }
+}
+
+// OutT = int32_t stores the raw ring sum (the accumulator between chunked
+// correction launches); float / uint16_t (bf16) / __half dequantise.
+template <typename OutT>
+__device__ __forceinline__ OutT secagg_finish(uint32_t s, float inv_scale) {
+  if constexpr (std::is_same_v<OutT, int32_t>) {
+    return (int32_t)s;
+  } else {
+    return from_f32<OutT>((float)(int32_t)s * inv_scale);  // v_cvt: RNE
+  }
+}
+
+// `out` may alias an input (the in-place int32 accumulator): every lane
+// reads exactly the elements it writes, so neither side is __restrict__.
+template <typename OutT, int EPL>
+__global__ void secagg_aggregate_kernel(OutT* out, SecaggInputs ins,
+                                        unsigned long long n,
+                                        unsigned long long blk0, uint32_t n0,
+                                        uint32_t n1, float inv_scale,
+                                        SecaggKeys corr, bool vec_ok) {
+  static_assert(EPL == 4 || EPL == 16, "4 (streaming) or 16 (ChaCha block)");
+  const unsigned long long nchunk = (n + EPL - 1ull) / EPL;
+  const unsigned long long stride =
+      (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long b =
+           (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+       b < nchunk; b += stride) {
+    const unsigned long long base = b * EPL;
+    const bool full = base + EPL <= n;
+    const bool vec = vec_ok && full;
+    const int cnt = full ? EPL : (int)(n - base);
+    uint32_t acc[EPL];
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) acc[i] = 0u;
+    for (int j = 0; j < ins.k; ++j) {
+      const int32_t* in = ins.in[j];
+      if (vec) {
+#pragma unroll
+        for (int v = 0; v < EPL / 4; ++v) {
+          const uint4 raw = reinterpret_cast<const uint4*>(in + base)[v];
+          acc[4 * v] += raw.x;
+          acc[4 * v + 1] += raw.y;
+          acc[4 * v + 2] += raw.z;
+          acc[4 * v + 3] += raw.w;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i)
+          if (i < cnt) acc[i] += (uint32_t)in[base + i];
+      }
+    }
+    if constexpr (EPL == 16) {
+      secagg_apply_keys<true>(corr, (uint32_t)(blk0 + b), n0, n1, acc);
+    }
+    if (vec) {
+      // EPL*sizeof(OutT) is 8 (one 8-byte store) or a multiple of 16.
+      alignas(16) OutT tmp[EPL];
+#pragma unroll
+      for (int i = 0; i < EPL; ++i)
+        tmp[i] = secagg_finish<OutT>(acc[i], inv_scale);
+      constexpr int kBytes = EPL * (int)sizeof(OutT);
+      if constexpr (kBytes % 16 == 0) {
+#pragma unroll
+        for (int v = 0; v < kBytes / 16; ++v)
+          reinterpret_cast<uint4*>(out + base)[v] =
+              reinterpret_cast<const uint4*>(tmp)[v];
+      } else {
+        static_assert(kBytes == 8, "unexpected store width");
+        *reinterpret_cast<uint2*>(out + base) =
+            *reinterpret_cast<const uint2*>(tmp);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < EPL; ++i)
+        if (i < cnt) out[base + i] = secagg_finish<OutT>(acc[i], inv_scale);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host wrappers
+// ---------------------------------------------------------------------------
+inline void secagg_check_range(const char* who, unsigned long long n,
+                               int64_t offset, int64_t frac_bits) {
+  TORCH_CHECK(frac_bits >= 0 && frac_bits <= kSecaggMaxFracBits, who,
+              ": frac_bits must be in [0, 30]");
+  TORCH_CHECK(offset >= 0 && offset % 16 == 0, who,
+              ": offset must be a non-negative multiple of 16");
+  TORCH_CHECK((unsigned long long)offset <= kSecaggMaxElements &&
+                  n <= kSecaggMaxElements - (unsigned long long)offset,
+              who, ": offset + n exceeds 2^36 (ChaCha20 counter would wrap)");
+}
+
+// Fill `dst` from rows [lo, lo+cnt) of a CPU uint8[K,32] / int32[K] pair.
+inline void secagg_fill_keys(SecaggKeys& dst, const torch::Tensor& keys,
+                             const torch::Tensor& signs, int64_t lo,
+                             int64_t cnt) {
+  dst.k = (int)cnt;
+  const uint8_t* kp = keys.data_ptr<uint8_t>() + lo * 32;
+  const int32_t* sp = signs.data_ptr<int32_t>() + lo;
+  for (int64_t j = 0; j < cnt; ++j) {
+    for (int w = 0; w < 8; ++w) {
+      const uint8_t* p = kp + j * 32 + w * 4;
+      dst.key[j][w] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) |
+                      ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    }
+    dst.sign[j] = sp[j];
+  }
+}
+
+inline void secagg_check_keys(const char* who, const torch::Tensor& keys,
+                              const torch::Tensor& signs) {
+  TORCH_CHECK(!keys.is_cuda() && keys.dtype() == torch::kUInt8 &&
+                  keys.is_contiguous() && keys.dim() == 2 &&
+                  keys.size(1) == 32,
+              who, ": keys must be a contiguous CPU uint8[K,32] tensor");
+  TORCH_CHECK(!signs.is_cuda() && signs.dtype() == torch::kInt32 &&
+                  signs.is_contiguous() && signs.dim() == 1 &&
+                  signs.size(0) == keys.size(0),
+              who, ": signs must be a contiguous CPU int32[K] tensor");
+  const int32_t* sp = signs.data_ptr<int32_t>();
+  for (int64_t j = 0; j < signs.size(0); ++j)
+    TORCH_CHECK(sp[j] == 1 || sp[j] == -1, who, ": signs must be +1 or -1");
+}
+
+inline bool secagg_aligned16(const void* p) {
+  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+
+// Enough workgroups to fill 256 CUs; the kernels grid-stride beyond that.
+inline int secagg_grid(unsigned long long items) {
+  const unsigned long long want = (items + kBlock - 1) / kBlock;
+  return (int)std::min<unsigned long long>(
+      4096ull, std::max<unsigned long long>(1ull, want));
+}
+
+void secagg_mask_async(torch::Tensor x, torch::Tensor out, torch::Tensor keys,
+                       torch::Tensor signs, uint64_t round, int64_t offset,
+                       double weight, int64_t frac_bits) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
+              "secagg_mask: x must be CUDA contiguous");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+                  out.dtype() == torch::kInt32 &&
+                  out.numel() == x.numel() && out.device() == x.device(),
+              "secagg_mask: out must be a contiguous int32 tensor of x's "
+              "length on x's device");
+  secagg_check_keys("secagg_mask", keys, signs);
+  TORCH_CHECK(keys.size(0) <= kSecaggMaxKeys - 1,
+              "secagg_mask: at most 15 peers");
+  const unsigned long long n = x.numel();
+  secagg_check_range("secagg_mask", n, offset, frac_bits);
+  if (n == 0) return;
+  SecaggKeys k{};
+  secagg_fill_keys(k, keys, signs, 0, keys.size(0));
+  const bool vec_ok =
+      secagg_aligned16(x.data_ptr()) && secagg_aligned16(out.data_ptr());
+  const unsigned long long blk0 = (unsigned long long)offset / 16ull;
+  const uint32_t n0 = (uint32_t)(round & 0xffffffffull);
+  const uint32_t n1 = (uint32_t)(round >> 32);
+  const float w = (float)weight;
+  const float scale = (float)(1ull << frac_bits);
+  const int blocks = secagg_grid((n + 15ull) / 16ull);
+  auto stream = at::hip::getCurrentHIPStream();
+  int32_t* o = out.data_ptr<int32_t>();
+  if (x.dtype() == torch::kBFloat16) {
+    hipLaunchKernelGGL((secagg_mask_kernel<uint16_t>), dim3(blocks),
+                       dim3(kBlock), 0, stream,
+                       reinterpret_cast<const uint16_t*>(x.data_ptr()), o, n,
+                       blk0, n0, n1, w, scale, k, vec_ok);
+  } else if (x.dtype() == torch::kHalf) {
+    hipLaunchKernelGGL((secagg_mask_kernel<__half>), dim3(blocks),
+                       dim3(kBlock), 0, stream,
+                       reinterpret_cast<const __half*>(x.data_ptr()), o, n,
+                       blk0, n0, n1, w, scale, k, vec_ok);
+  } else if (x.dtype() == torch::kFloat) {
+    hipLaunchKernelGGL((secagg_mask_kernel<float>), dim3(blocks), dim3(kBlock),
+                       0, stream, x.data_ptr<float>(), o, n, blk0, n0, n1, w,
+                       scale, k, vec_ok);
+  } else {
+    TORCH_CHECK(false, "secagg_mask: unsupported dtype ", x.dtype());
+  }
+}
+
+template <typename OutT, int EPL>
+void secagg_launch_aggregate(OutT* out, const SecaggInputs& ins,
+                             unsigned long long n, unsigned long long blk0,
+                             uint32_t n0, uint32_t n1, float inv_scale,
+                             const SecaggKeys& corr, bool vec_ok,
+                             hipStream_t stream) {
+  const int blocks = secagg_grid((n + EPL - 1ull) / EPL);
+  hipLaunchKernelGGL((secagg_aggregate_kernel<OutT, EPL>), dim3(blocks),
+                     dim3(kBlock), 0, stream, out, ins, n, blk0, n0, n1,
+                     inv_scale, corr, vec_ok);
+}
+
+template <typename OutT>
+void secagg_launch_final(OutT* out, const SecaggInputs& ins,
+                         unsigned long long n, unsigned long long blk0,
+                         uint32_t n0, uint32_t n1, float inv_scale,
+                         const SecaggKeys& corr, bool vec_ok,
+                         hipStream_t stream) {
+  if (corr.k == 0) {
+    secagg_launch_aggregate<OutT, 4>(out, ins, n, blk0, n0, n1, inv_scale,
+                                     corr, vec_ok, stream);
+  } else {
+    secagg_launch_aggregate<OutT, 16>(out, ins, n, blk0, n0, n1, inv_scale,
+                                      corr, vec_ok, stream);
+  }
+}
+
+void secagg_aggregate_async(torch::Tensor out,
+                            std::vector<torch::Tensor> inputs,
+                            torch::Tensor corr_keys, torch::Tensor corr_signs,
+                            uint64_t round, int64_t offset,
+                            int64_t frac_bits) {
+  TORCH_CHECK(!inputs.empty() && inputs.size() <= kMaxInputs,
+              "secagg_aggregate: 1..16 inputs");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous(),
+              "secagg_aggregate: out must be CUDA contiguous");
+  secagg_check_keys("secagg_aggregate", corr_keys, corr_signs);
+  const unsigned long long n = out.numel();
+  secagg_check_range("secagg_aggregate", n, offset, frac_bits);
+  TORCH_CHECK(out.dtype() == torch::kFloat || out.dtype() == torch::kHalf ||
+                  out.dtype() == torch::kBFloat16,
+              "secagg_aggregate: unsupported out dtype ", out.dtype());
+  SecaggInputs ins;
+  ins.k = (int)inputs.size();
+  bool vec_ok = secagg_aligned16(out.data_ptr());
+  for (int j = 0; j < ins.k; ++j) {
+    TORCH_CHECK(inputs[j].is_cuda() && inputs[j].is_contiguous() &&
+                    inputs[j].numel() == (long long)n &&
+                    inputs[j].dtype() == torch::kInt32 &&
+                    inputs[j].device() == out.device(),
+                "secagg_aggregate: input ", j, " mismatch");
+    ins.in[j] = inputs[j].data_ptr<int32_t>();
+    vec_ok = vec_ok && secagg_aligned16(ins.in[j]);
+  }
+  if (n == 0) return;
+  const unsigned long long blk0 = (unsigned long long)offset / 16ull;
+  const uint32_t n0 = (uint32_t)(round & 0xffffffffull);
+  const uint32_t n1 = (uint32_t)(round >> 32);
+  const float inv_scale = 1.0f / (float)(1ull << frac_bits);
+  auto stream = at::hip::getCurrentHIPStream();
+
+  // More corrections than one argument block holds: fold all but the last
+  // chunk into an int32 ring accumulator, in place after the first launch.
+  const int64_t C = corr_keys.size(0);
+  int64_t done = 0;
+  SecaggKeys corr{};
+  torch::Tensor acc;
+  while (C - done > kSecaggMaxKeys) {
+    secagg_fill_keys(corr, corr_keys, corr_signs, done, kSecaggMaxKeys);
+    if (!acc.defined()) {
+      acc = torch::empty({(long long)n},
+                         torch::dtype(torch::kInt32).device(out.device()));
+    }
+    secagg_launch_aggregate<int32_t, 16>(
+        acc.data_ptr<int32_t>(), ins, n, blk0, n0, n1, 0.0f, corr,
+        vec_ok && secagg_aligned16(acc.data_ptr()), stream);
+    ins.k = 1;
+    ins.in[0] = acc.data_ptr<int32_t>();
+    vec_ok = secagg_aligned16(out.data_ptr()) &&
+             secagg_aligned16(acc.data_ptr());
+    done += kSecaggMaxKeys;
+  }
+  secagg_fill_keys(corr, corr_keys, corr_signs, done, C - done);
+  if (out.dtype() == torch::kBFloat16) {
+    secagg_launch_final<uint16_t>(reinterpret_cast<uint16_t*>(out.data_ptr()),
+                                  ins, n, blk0, n0, n1, inv_scale, corr,
+                                  vec_ok, stream);
+  } else if (out.dtype() == torch::kHalf) {
+    secagg_launch_final<__half>(reinterpret_cast<__half*>(out.data_ptr()), ins,
+                                n, blk0, n0, n1, inv_scale, corr, vec_ok,
+                                stream);
+  } else {
+    secagg_launch_final<float>(out.data_ptr<float>(), ins, n, blk0, n0, n1,
+                               inv_scale, corr, vec_ok, stream);
+  }
+}

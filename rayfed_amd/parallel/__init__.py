@@ -1,2 +1,8 @@
 """Intra-party parallelism: RCCL-over-xGMI process groups and FedAvg
-aggregation."""
+aggregation, plus pairwise-mask secure aggregation
+across parties (``secagg``)."""
+from rayfed_amd.parallel.secagg import (  # noqa: F401
+    SecAggSession,
+    aggregate,
+    derive_pair_key,
+)
