@@ -194,14 +194,14 @@ __device__ __forceinline__ float bf16_to_f32(uint16_t h) {
 }
 
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-  union {
-    uint32_t u;
-    float f;
-  } c;
-  c.f = f;
-  // round-to-nearest-even
-  uint32_t r = c.u + 0x7FFFu + ((c.u >> 16) & 1u);
-  return (uint16_t)(r >> 16);
+  // Round to nearest even with the hardware convert (v_cvt_pk_bf16_f32):
+  // one instruction, and NaN stays NaN.  The integer form
+  // (u + 0x7FFF + lsb) >> 16 carries a high-mantissa NaN such as 0x7FFFFFFF
+  // over into the sign bit (-> -0).
+  const __bf16 h = (__bf16)f;
+  uint16_t r;
+  __builtin_memcpy(&r, &h, sizeof(r));
+  return r;
 }
 
 // ---------------------------------------------------------------------------
@@ -310,7 +310,9 @@ __global__ void hash64_kernel(const unsigned long long* __restrict__ words,
 // ---------------------------------------------------------------------------
 // Fused FedAvg combine + integrity hash (zero-copy receive path).
 //
-// out[i] = wa*local[i] + wb*peer[i] (bf16, fp32 math) while computing the
+// out[i] = fma(wa, local[i], wb*peer[i]) (bf16, fp32 math; written as an
+// explicit fmaf so the rounding does not hang on the compiler's contraction
+// choice) while computing the
 // hash64 of the PEER bytes in the same pass — the receiver combines
 // directly from the sender's IPC slab, never materializing a copy and
 // never re-reading it for the verify.  The thread/word mapping is
@@ -349,7 +351,7 @@ __global__ void fedavg_combine_hash_kernel(
         for (int e = 0; e < 4; ++e) {
           const float p = bf16_to_f32((uint16_t)(pw[k] >> (16 * e)));
           const float l = bf16_to_f32((uint16_t)(lv >> (16 * e)));
-          o |= (unsigned long long)f32_to_bf16(wa * l + wb * p) << (16 * e);
+          o |= (unsigned long long)f32_to_bf16(fmaf(wa, l, wb * p)) << (16 * e);
         }
         ow[k] = o;
       }
@@ -366,7 +368,7 @@ __global__ void fedavg_combine_hash_kernel(
         for (int e = 0; e < 4; ++e) {
           const float p = bf16_to_f32((uint16_t)(pw >> (16 * e)));
           const float l = bf16_to_f32((uint16_t)(lv >> (16 * e)));
-          o |= (unsigned long long)f32_to_bf16(wa * l + wb * p) << (16 * e);
+          o |= (unsigned long long)f32_to_bf16(fmaf(wa, l, wb * p)) << (16 * e);
         }
         reinterpret_cast<unsigned long long*>(out)[i] = o;
       }
@@ -387,7 +389,7 @@ __global__ void fedavg_combine_hash_kernel(
         const float p = bf16_to_f32(
             (uint16_t)(peer_tail[2 * e] | (peer_tail[2 * e + 1] << 8)));
         const float l = bf16_to_f32(local[e0 + e]);
-        out[e0 + e] = f32_to_bf16(wa * l + wb * p);
+        out[e0 + e] = f32_to_bf16(fmaf(wa, l, wb * p));
       }
     }
     v ^= fmix64((nbytes * kFnvP) ^ kFnvOff);
@@ -412,9 +414,16 @@ __global__ void crc_finalize_kernel(uint32_t* out, TailParam p) {
 // ---------------------------------------------------------------------------
 // fp8 wire cast (OCP e4m3), fused with CRC over the produced bytes
 // ---------------------------------------------------------------------------
+// Wire contract (CPU reference: rayfed_amd/ops/fp8_ref.py): round to nearest
+// even, finite |x| > 448 saturates to 0x7E/0xFE, +-Inf and NaN become the NaN
+// byte sign|0x7F.  The non-finite case is decided here, not by the hardware
+// convert: on gfx950 that maps +-Inf to 0x7F/0xFF but every NaN to 0xFF.
 __device__ __forceinline__ uint8_t f32_to_fp8(float f) {
+  const uint32_t u = __float_as_uint(f);
   __hip_fp8_e4m3 v(f);
-  return v.__x;
+  // (u >> 24) | 0x7F == sign | 0x7F; a select, not a branch.
+  return ((u & 0x7F800000u) == 0x7F800000u) ? (uint8_t)((u >> 24) | 0x7Fu)
+                                             : (uint8_t)v.__x;
 }
 
 __device__ __forceinline__ float fp8_to_f32(uint8_t b) {
@@ -425,6 +434,10 @@ __device__ __forceinline__ float fp8_to_f32(uint8_t b) {
 
 // src: bf16 elements; dst: fp8 bytes.  Thread t produces kSubLen output
 // bytes (= kSubLen input bf16 elements); same combine scheme as crc32_kernel.
+// kVec: src is 16-byte and dst 8-byte aligned (decided on the host; slice
+// offsets are multiples of kSubLen so one answer holds for every thread).
+// Otherwise every element takes the scalar loop.
+template <bool kVec>
 __global__ void pack_fp8_kernel(const uint16_t* __restrict__ src,
                                 uint8_t* __restrict__ dst,
                                 unsigned long long n_elems, uint32_t T,
@@ -446,7 +459,7 @@ __global__ void pack_fp8_kernel(const uint16_t* __restrict__ src,
     const uint16_t* p = src + off;
     uint8_t* q = dst + off;
     uint32_t i = 0;
-    for (; i + 8 <= len; i += 8) {
+    for (; kVec && i + 8 <= len; i += 8) {
       const uint4 v = *reinterpret_cast<const uint4*>(p + i);  // 8 bf16
       uint32_t lo = 0, hi = 0;
       lo |= (uint32_t)f32_to_fp8(bf16_to_f32((uint16_t)(v.x & 0xFFFFu)));
@@ -594,6 +607,8 @@ __global__ void unpack_fp8_hash64_kernel(
   block_xor_out64(v, out, lds);
 }
 
+// kVec: src is 8-byte and dst 16-byte aligned (decided on the host).
+template <bool kVec>
 __global__ void unpack_fp8_kernel(const uint8_t* __restrict__ src,
                                   uint16_t* __restrict__ dst,
                                   unsigned long long n_elems) {
@@ -602,7 +617,7 @@ __global__ void unpack_fp8_kernel(const uint8_t* __restrict__ src,
   for (unsigned long long base =
            ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * 8ull;
        base < n_elems; base += stride) {
-    if (base + 8 <= n_elems) {
+    if (kVec && base + 8 <= n_elems) {
       const uint2 v = *reinterpret_cast<const uint2*>(src + base);
       uint4 o;
       o.x = (uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.x))) |
@@ -615,7 +630,9 @@ __global__ void unpack_fp8_kernel(const uint8_t* __restrict__ src,
             ((uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.y >> 24))) << 16);
       *reinterpret_cast<uint4*>(dst + base) = o;
     } else {
-      for (unsigned long long i = base; i < n_elems; ++i)
+      const unsigned long long end =
+          base + 8 <= n_elems ? base + 8 : n_elems;
+      for (unsigned long long i = base; i < end; ++i)
         dst[i] = f32_to_bf16(fp8_to_f32(src[i]));
     }
   }
@@ -662,8 +679,10 @@ __device__ __forceinline__ float from_f32<float>(float v) {
   return v;
 }
 
-// VEC elements per lane per iteration, sized to 16-byte loads.
-template <typename T, int VEC>
+// VEC elements per lane per iteration, sized to 16-byte loads.  kVec: out and
+// every input are 16-byte aligned (decided on the host); otherwise each lane
+// walks its VEC elements with scalar accesses — same values, same order.
+template <typename T, int VEC, bool kVec>
 __global__ void fedavg_reduce_kernel(T* __restrict__ out, ReduceArgs args,
                                      unsigned long long n) {
   const unsigned long long stride =
@@ -674,7 +693,8 @@ __global__ void fedavg_reduce_kernel(T* __restrict__ out, ReduceArgs args,
     float acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
-    const bool full = base + VEC <= n;
+    const bool full = kVec && base + VEC <= n;
+    const unsigned long long end = base + VEC <= n ? base + VEC : n;
     for (int j = 0; j < args.k; ++j) {
       const T* in = reinterpret_cast<const T*>(args.in[j]);
       const float w = args.w[j];
@@ -686,7 +706,7 @@ __global__ void fedavg_reduce_kernel(T* __restrict__ out, ReduceArgs args,
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] += w * to_f32<T>(e[v]);
       } else {
-        for (unsigned long long i = base; i < n; ++i)
+        for (unsigned long long i = base; i < end; ++i)
           acc[i - base] += w * to_f32<T>(in[i]);
       }
     }
@@ -696,7 +716,7 @@ __global__ void fedavg_reduce_kernel(T* __restrict__ out, ReduceArgs args,
       for (int v = 0; v < VEC; ++v) tmp[v] = from_f32<T>(acc[v]);
       *reinterpret_cast<uint4*>(out + base) = *reinterpret_cast<uint4*>(tmp);
     } else {
-      for (unsigned long long i = base; i < n; ++i)
+      for (unsigned long long i = base; i < end; ++i)
         out[i] = from_f32<T>(acc[i - base]);
     }
   }
@@ -831,6 +851,10 @@ TailParam make_tail_param(unsigned long long n, uint32_t T) {
   return p;
 }
 
+inline bool aligned_to(const void* p, uintptr_t bytes) {
+  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
+}
+
 inline uint32_t n_threads_for(unsigned long long nbytes) {
   return (uint32_t)((nbytes + kSubLen - 1) / kSubLen);
 }
@@ -922,6 +946,9 @@ torch::Tensor pack_crc_async(torch::Tensor src, torch::Tensor dst) {
   TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kUInt8 &&
                   dst.is_contiguous() && dst.numel() >= src.numel(),
               "pack_crc dst too small");
+  // The kernel picks 16-byte loads AND stores from src's alignment alone.
+  TORCH_CHECK(!aligned_to(src.data_ptr(), 16) || aligned_to(dst.data_ptr(), 16),
+              "pack_crc: dst must be 16-byte aligned when src is");
   const unsigned long long n = src.numel();
   auto out = torch::zeros(
       {3}, torch::dtype(torch::kInt32).device(src.device()));
@@ -945,7 +972,7 @@ torch::Tensor pack_fp8_async(torch::Tensor src, torch::Tensor dst) {
                   src.is_contiguous(),
               "pack_fp8 expects contiguous CUDA bf16 src");
   TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kUInt8 &&
-                  dst.numel() >= src.numel(),
+                  dst.is_contiguous() && dst.numel() >= src.numel(),
               "pack_fp8 dst too small");
   const unsigned long long n = src.numel();
   auto out = torch::zeros(
@@ -955,7 +982,12 @@ torch::Tensor pack_fp8_async(torch::Tensor src, torch::Tensor dst) {
   const uint32_t T = n_threads_for(n);
   const uint32_t blocks = (T + kBlock - 1) / kBlock;
   auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(pack_fp8_kernel, dim3(blocks), dim3(kBlock), 0, stream,
+  // uint4 loads of src / uint2 stores of dst need 16 / 8-byte alignment;
+  // views at odd element offsets take the scalar instantiation.
+  const bool vec =
+      aligned_to(src.data_ptr(), 16) && aligned_to(dst.data_ptr(), 8);
+  hipLaunchKernelGGL(vec ? pack_fp8_kernel<true> : pack_fp8_kernel<false>,
+                     dim3(blocks), dim3(kBlock), 0, stream,
                      reinterpret_cast<const uint16_t*>(src.data_ptr()),
                      dst.data_ptr<uint8_t>(), n, T, consts.tables, consts.pows,
                      consts.halfmat,
@@ -1032,7 +1064,10 @@ void unpack_fp8_async(torch::Tensor src, torch::Tensor dst) {
   const uint32_t blocks =
       std::min<unsigned long long>(4096ull, (n / 8 + kBlock - 1) / kBlock + 1);
   auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(unpack_fp8_kernel, dim3(blocks), dim3(kBlock), 0, stream,
+  const bool vec =
+      aligned_to(src.data_ptr(), 8) && aligned_to(dst.data_ptr(), 16);
+  hipLaunchKernelGGL(vec ? unpack_fp8_kernel<true> : unpack_fp8_kernel<false>,
+                     dim3(blocks), dim3(kBlock), 0, stream,
                      src.data_ptr<uint8_t>(),
                      reinterpret_cast<uint16_t*>(dst.data_ptr()), n);
 }
@@ -1083,6 +1118,9 @@ void fedavg_reduce_(torch::Tensor out, std::vector<torch::Tensor> inputs,
   const unsigned long long n = out.numel();
   ReduceArgs args;
   args.k = (int)inputs.size();
+  // The kernel's uint4 accesses need every pointer 16-byte aligned; slices
+  // of a flat buffer at odd element offsets take the scalar instantiation.
+  bool vec = aligned_to(out.data_ptr(), 16);
   for (int j = 0; j < args.k; ++j) {
     TORCH_CHECK(inputs[j].is_cuda() && inputs[j].is_contiguous() &&
                     inputs[j].numel() == (long long)n &&
@@ -1090,20 +1128,27 @@ void fedavg_reduce_(torch::Tensor out, std::vector<torch::Tensor> inputs,
                 "input ", j, " mismatch");
     args.in[j] = inputs[j].data_ptr();
     args.w[j] = (float)weights[j];
+    vec = vec && aligned_to(args.in[j], 16);
   }
   auto stream = at::hip::getCurrentHIPStream();
   // >= 2048 workgroups to fill 256 CUs across 8 XCDs (guide §1).
   const int blocks = 4096;
   if (out.dtype() == torch::kBFloat16) {
-    hipLaunchKernelGGL((fedavg_reduce_kernel<uint16_t, 8>), dim3(blocks),
+    hipLaunchKernelGGL((vec ? fedavg_reduce_kernel<uint16_t, 8, true>
+                            : fedavg_reduce_kernel<uint16_t, 8, false>),
+                       dim3(blocks),
                        dim3(kBlock), 0, stream,
                        reinterpret_cast<uint16_t*>(out.data_ptr()), args, n);
   } else if (out.dtype() == torch::kHalf) {
-    hipLaunchKernelGGL((fedavg_reduce_kernel<__half, 8>), dim3(blocks),
+    hipLaunchKernelGGL((vec ? fedavg_reduce_kernel<__half, 8, true>
+                            : fedavg_reduce_kernel<__half, 8, false>),
+                       dim3(blocks),
                        dim3(kBlock), 0, stream,
                        reinterpret_cast<__half*>(out.data_ptr()), args, n);
   } else if (out.dtype() == torch::kFloat) {
-    hipLaunchKernelGGL((fedavg_reduce_kernel<float, 4>), dim3(blocks),
+    hipLaunchKernelGGL((vec ? fedavg_reduce_kernel<float, 4, true>
+                            : fedavg_reduce_kernel<float, 4, false>),
+                       dim3(blocks),
                        dim3(kBlock), 0, stream, out.data_ptr<float>(), args, n);
   } else {
     TORCH_CHECK(false, "fedavg_reduce_: unsupported dtype ", out.dtype());
@@ -1138,9 +1183,13 @@ void fedavg_reduce_mfma_(torch::Tensor out, std::vector<torch::Tensor> inputs,
 }
 
 void masked_add_(torch::Tensor dst, torch::Tensor src, torch::Tensor mask) {
-  TORCH_CHECK(dst.is_cuda() && dst.is_contiguous() && src.is_contiguous() &&
+  TORCH_CHECK(dst.is_cuda() && src.is_cuda() && mask.is_cuda() &&
+                  dst.is_contiguous() && src.is_contiguous() &&
                   mask.is_contiguous(),
               "masked_add_: contiguous CUDA tensors required");
+  TORCH_CHECK(src.dtype() == dst.dtype(),
+              "masked_add_: src dtype ", src.dtype(), " != dst dtype ",
+              dst.dtype());
   TORCH_CHECK(src.numel() == dst.numel() && mask.numel() == dst.numel(),
               "masked_add_: size mismatch");
   TORCH_CHECK(mask.dtype() == torch::kUInt8 || mask.dtype() == torch::kBool,
