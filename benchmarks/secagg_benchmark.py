@@ -10,12 +10,23 @@ Times, with device events around each call after a warm-up:
     16-byte loads and one 16-byte store per lane) and less arithmetic.
     The two are timed alternately, call by call, so drift hits both.
 
+Then the differential-privacy kernels (``--sections dp`` runs only these):
+
+  * ``secagg_mask_noise_async`` at W = 4 words per element for 1, 3 and 7
+    peers on bf16 and fp32 input, each against the yardstick
+    ``secagg_mask_async`` at ``peers + 4`` (the same number of ChaCha20
+    blocks per 16 elements), interleaved call by call;
+  * ``sumsq_async`` on bf16 and fp32 against ``hash64_async`` over the same
+    bytes — the project's read-only streaming pass.
+
 Bytes are the compulsory traffic computed from the shapes (inputs read once,
 output written once).  One JSON line per configuration, then the
-aggregate/fedavg bandwidth ratio per K with the repeat-to-repeat spread.
+aggregate/fedavg bandwidth ratio per K with the repeat-to-repeat spread; the
+DP rows carry their time ratio against the yardstick and both spreads.
 
     python benchmarks/secagg_benchmark.py [--n 67108864] [--warmup 5]
                                           [--repeats 50]
+                                          [--sections all|secagg|dp]
 
 The default n (64 Mi elements: 256 MiB per fp32/int32 tensor) is past the
 4 MiB L2 and, for every multi-tensor configuration, the 256 MiB Infinity
@@ -78,11 +89,77 @@ def _stats(ms, nbytes):
     }
 
 
+def _ratio(name, extra, t_new, t_ref):
+    """Time ratio new/yardstick (> 1: the new kernel is slower), per-pair
+    range, and the fastest-to-slowest spread of each side's repeats."""
+    per_pair = [a / b for a, b in zip(t_new, t_ref)]
+    rec = {"op": name}
+    rec.update(extra)
+    rec.update({
+        "time_ratio_median": round(
+            statistics.median(t_new) / statistics.median(t_ref), 4),
+        "time_ratio_pairs_min": round(min(per_pair), 4),
+        "time_ratio_pairs_max": round(max(per_pair), 4),
+        "yardstick_spread": round(max(t_ref) / min(t_ref) - 1.0, 4),
+        "new_spread": round(max(t_new) / min(t_new) - 1.0, 4),
+    })
+    return rec
+
+
+def _dp_section(ext, n, dev, args):
+    words = 4
+    noise_key = torch.from_numpy(np.frombuffer(
+        hashlib.sha256(b"bench-noise").digest(), dtype=np.uint8).copy())
+    out_a = torch.empty(n, dtype=torch.int32, device=dev)
+    out_b = torch.empty(n, dtype=torch.int32, device=dev)
+    for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "fp32")):
+        x = torch.randn(n, device=dev).to(dtype)
+        nbytes = n * (x.element_size() + 4)
+        for peers in (1, 3, 7):
+            kt, st = _keys(peers)
+            ky, sy = _keys(peers + words)
+            t_noise, t_mask = _time_calls(
+                [lambda: ext.secagg_mask_noise_async(
+                    x, out_a, kt, st, noise_key, words, 1000, ROUND, 0, 1.0,
+                    FRAC_BITS),
+                 lambda: ext.secagg_mask_async(x, out_b, ky, sy, ROUND, 0,
+                                               1.0, FRAC_BITS)],
+                args.warmup, args.repeats)
+            rec = {"op": "mask+noise", "dtype": name, "peers": peers,
+                   "words": words, "bytes": nbytes}
+            rec.update(_stats(t_noise, nbytes))
+            rec["gelem_per_s"] = round(
+                n / statistics.median(t_noise) / 1e6, 2)
+            print(json.dumps(rec), flush=True)
+            rec = {"op": "mask", "dtype": name, "peers": peers + words,
+                   "bytes": nbytes, "yardstick_for": "mask+noise"}
+            rec.update(_stats(t_mask, nbytes))
+            print(json.dumps(rec), flush=True)
+            print(json.dumps(_ratio(
+                "mask+noise_over_mask_at_peers_plus_words",
+                {"dtype": name, "peers": peers, "words": words},
+                t_noise, t_mask)), flush=True)
+        nbytes = n * x.element_size()
+        xb = x.view(torch.uint8)
+        t_sq, t_hash = _time_calls(
+            [lambda: ext.sumsq_async(x), lambda: ext.hash64_async(xb)],
+            args.warmup, args.repeats)
+        for op, ms in (("sumsq", t_sq), ("hash64", t_hash)):
+            rec = {"op": op, "dtype": name, "bytes": nbytes}
+            rec.update(_stats(ms, nbytes))
+            print(json.dumps(rec), flush=True)
+        print(json.dumps(_ratio("sumsq_over_hash64", {"dtype": name},
+                                t_sq, t_hash)), flush=True)
+        del x, xb
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--n", type=int, default=1 << 26, help="elements")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=50)
+    ap.add_argument("--sections", choices=("all", "secagg", "dp"),
+                    default="all")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("secagg_benchmark needs a GPU")
@@ -95,6 +172,13 @@ def main():
                       "repeats": args.repeats,
                       "device": torch.cuda.get_device_name(0)}))
 
+    if args.sections != "dp":
+        _secagg_section(ext, n, dev, args)
+    if args.sections != "secagg":
+        _dp_section(ext, n, dev, args)
+
+
+def _secagg_section(ext, n, dev, args):
     # ---- mask ------------------------------------------------------------
     out_i32 = torch.empty(n, dtype=torch.int32, device=dev)
     for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "fp32")):

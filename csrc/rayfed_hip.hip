@@ -19,6 +19,8 @@
 //     HBM-bound, always vectorize).
 //   * secagg_mask / secagg_aggregate — secure aggregation in Z/2^32 with
 //     in-register ChaCha20 pairwise masks (secagg_kernels.h).
+//   * secagg_mask_noise / sumsq — differential privacy on top of it: L2
+//     norm for clipping and binomial noise generated inside the mask pass.
 //
 // Wavefront size is 64 on CDNA4 (not 32); reductions below use width-64
 // shuffles.  Compiled for gfx950 only — no CUDA shims, no multi-arch.
@@ -1309,6 +1311,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("secagg_aggregate_async", &secagg_aggregate_async,
         "out = dequantise(ring-sum of int32 inputs - signed ChaCha20 "
         "corrections of dropped parties)");
+  m.def("secagg_mask_noise_async", &secagg_mask_noise_async,
+        "secagg_mask_async plus on-device binomial noise: step * (popcount "
+        "of `words` words of the noise key's ChaCha20 stream - 16*words) per "
+        "element (differential privacy; same spec module)",
+        pybind11::arg("x"), pybind11::arg("out"), pybind11::arg("keys"),
+        pybind11::arg("signs"), pybind11::arg("noise_key"),
+        pybind11::arg("words"), pybind11::arg("step"), pybind11::arg("round"),
+        pybind11::arg("offset"), pybind11::arg("weight"),
+        pybind11::arg("frac_bits"), pybind11::arg("max_blocks") = 0);
+  m.def("sumsq_async", &sumsq_async,
+        "float64 sum of squares of an fp32/bf16/fp16 tensor -> double[1] "
+        "device tensor (per-block partials, no atomics: reproducible)");
   m.def("crc32_combine", &crc32_combine_py, "zlib-style CRC combine");
   m.def("host_register", &host_register, "hipHostRegister an existing mapping");
   m.def("host_unregister", &host_unregister, "hipHostUnregister");

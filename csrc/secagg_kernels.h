@@ -7,6 +7,11 @@
 //
 //   * secagg_mask_kernel<T>       sender: quantise fp32/bf16/fp16 to
 //     fixed point and add the signed ChaCha20 keystream of up to 15 peers.
+//   * secagg_mask_noise_kernel<T, W>  the same pass with on-device binomial
+//     noise (popcounts of a private ChaCha20 stream, W words per element)
+//     added before the masks — differential privacy.
+//   * sumsq_kernel<T>             float64 sum of squares (the L2 norm that
+//     clipping needs), per-block partials, no atomics.
 //   * secagg_aggregate_kernel<OutT, EPL>  aggregator: ring-sum of K int32
 //     inputs, subtract the residual keystreams of dropped parties,
 //     dequantise.  EPL = 4 is the pure streaming reduce (no corrections,
@@ -30,6 +35,15 @@ struct SecaggKeys {
   int k;
 };
 
+// Binomial-noise stream (differential privacy): the party's private key and
+// the third nonce word that separates it from every pair-mask keystream.
+constexpr uint32_t kSecaggNoiseNonce = 1u;
+constexpr int64_t kSecaggMaxNoiseStep = 1ll << 20;
+
+struct SecaggNoiseKey {
+  uint32_t key[8];  // little-endian key words
+};
+
 struct SecaggInputs {
   const int32_t* in[kMaxInputs];
   int k;
@@ -42,16 +56,19 @@ struct SecaggInputs {
   c += d; b ^= c; b = __builtin_rotateleft32(b, 7);
 
 // One ChaCha20 block (RFC 8439 §2.3 layout): counter `ctr`, nonce words
-// (n0, n1, 0).  `key` is wave-uniform.
+// (n0, n1, n2).  `key` is wave-uniform.  n2 is 0 for the pair-mask
+// keystream and kSecaggNoiseNonce for the noise stream; both are literals at
+// the call sites, so the pair-mask code is what it was with a fixed 0.
 __device__ __forceinline__ void chacha20_block(const uint32_t* key,
                                                uint32_t ctr, uint32_t n0,
-                                               uint32_t n1, uint32_t out[16]) {
+                                               uint32_t n1, uint32_t n2,
+                                               uint32_t out[16]) {
   const uint32_t c0 = 0x61707865u, c1 = 0x3320646eu, c2 = 0x79622d32u,
                  c3 = 0x6b206574u;
   uint32_t x0 = c0, x1 = c1, x2 = c2, x3 = c3;
   uint32_t x4 = key[0], x5 = key[1], x6 = key[2], x7 = key[3];
   uint32_t x8 = key[4], x9 = key[5], x10 = key[6], x11 = key[7];
-  uint32_t x12 = ctr, x13 = n0, x14 = n1, x15 = 0u;
+  uint32_t x12 = ctr, x13 = n0, x14 = n1, x15 = n2;
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
     SECAGG_QR(x0, x4, x8, x12)
@@ -70,7 +87,7 @@ __device__ __forceinline__ void chacha20_block(const uint32_t* key,
   out[8] = x8 + key[4];   out[9] = x9 + key[5];
   out[10] = x10 + key[6]; out[11] = x11 + key[7];
   out[12] = x12 + ctr;    out[13] = x13 + n0;
-  out[14] = x14 + n1;     out[15] = x15;
+  out[14] = x14 + n1;     out[15] = x15 + n2;
 }
 
 #undef SECAGG_QR
@@ -84,7 +101,7 @@ __device__ __forceinline__ void secagg_apply_keys(const SecaggKeys& keys,
                                                   uint32_t acc[16]) {
   for (int j = 0; j < keys.k; ++j) {
     uint32_t ks[16];
-    chacha20_block(keys.key[j], ctr, n0, n1, ks);
+    chacha20_block(keys.key[j], ctr, n0, n1, 0u, ks);
     if ((keys.sign[j] > 0) != kNegate) {  // wave-uniform branch
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] += ks[e];
@@ -165,6 +182,185 @@ __global__ void secagg_mask_kernel(const T* __restrict__ x,
         if (i < cnt) out[base + i] = (int32_t)acc[i];
     }
   }
+}
+
+// acc[i] += step * (sum_{t<W} popcount(NS(W*(16*blk + i) + t)) - 16*W) for the
+// 16 elements of block `blk`: the binomial noise of secagg_ref.py.  The
+// element's W words never straddle a ChaCha20 block, so noise block t (counter
+// W*blk + t) carries the words of elements [t*E, t*E + E), E = 16/W.  The
+// t loop stays rolled (one block function in the code); the uniform compare
+// `t == i / E` routes each sum to its accumulator with static register
+// indices only.
+template <int W>
+__device__ __forceinline__ void secagg_add_noise(const SecaggNoiseKey& nk,
+                                                 uint32_t blk, uint32_t n0,
+                                                 uint32_t n1, uint32_t step,
+                                                 uint32_t acc[16]) {
+  constexpr int E = 16 / W;  // elements per noise block
+  const uint32_t centre = 0u - 16u * (uint32_t)W * step;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] += centre;
+#pragma unroll 1
+  for (int t = 0; t < W; ++t) {
+    uint32_t ns[16];
+    chacha20_block(nk.key, (uint32_t)W * blk + (uint32_t)t, n0, n1,
+                   kSecaggNoiseNonce, ns);
+    uint32_t s[E];
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+      uint32_t c = 0;
+#pragma unroll
+      for (int j = 0; j < W; ++j)
+        c += (uint32_t)__builtin_popcount(ns[W * k + j]);
+      s[k] = c * step;
+    }
+    if constexpr (W == 1) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] += s[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] += (t == i / E) ? s[i % E] : 0u;
+    }
+  }
+}
+
+// secagg_mask_kernel plus on-device binomial noise (W keystream words per
+// element): same lane ownership, loads and stores; the un-noised quantised
+// update never reaches memory.  Noise counters W*(blk0 + b) + t, t < W.
+template <typename T, int W>
+__global__ void secagg_mask_noise_kernel(const T* __restrict__ x,
+                                         int32_t* __restrict__ out,
+                                         unsigned long long n,
+                                         unsigned long long blk0, uint32_t n0,
+                                         uint32_t n1, float weight,
+                                         float scale, SecaggKeys keys,
+                                         SecaggNoiseKey nkey, uint32_t step,
+                                         bool vec_ok) {
+  const unsigned long long nblk = (n + 15ull) / 16ull;
+  const unsigned long long stride =
+      (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long b =
+           (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+       b < nblk; b += stride) {
+    const unsigned long long base = b * 16ull;
+    const bool vec = vec_ok && (base + 16ull <= n);
+    const int cnt = (base + 16ull <= n) ? 16 : (int)(n - base);
+    uint32_t acc[16];
+    if (vec) {
+      constexpr int kLoads = (int)sizeof(T);  // 16 elements = sizeof(T) uint4
+      uint4 raw[kLoads];
+#pragma unroll
+      for (int v = 0; v < kLoads; ++v)
+        raw[v] = reinterpret_cast<const uint4*>(x + base)[v];
+      const T* e = reinterpret_cast<const T*>(raw);
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        acc[i] = secagg_quantize(to_f32<T>(e[i]), weight, scale);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        acc[i] = (i < cnt)
+                     ? secagg_quantize(to_f32<T>(x[base + i]), weight, scale)
+                     : 0u;
+    }
+    // (offset + n) * W <= 2^36 is validated: W*(blk0 + b) + t fits 32 bits.
+    secagg_add_noise<W>(nkey, (uint32_t)(blk0 + b), n0, n1, step, acc);
+    secagg_apply_keys<false>(keys, (uint32_t)(blk0 + b), n0, n1, acc);
+    if (vec) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        reinterpret_cast<uint4*>(out + base)[v] = make_uint4(
+            acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (i < cnt) out[base + i] = (int32_t)acc[i];
+    }
+  }
+}
+
+// Sum of squares for L2 clipping.  Each lane accumulates double(x)^2 in a
+// double (every square of an fp32/bf16/fp16 value is exact in double), the
+// wave reduces by shuffles, the block's four waves through LDS, and each
+// block writes one partial; sumsq_final_kernel adds the partials in a fixed
+// order.  No atomics: the result is reproducible run to run.
+__device__ __forceinline__ double sumsq_block_reduce(double v, double* wsum) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1)
+    v += __shfl_down(v, off, kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  if (lane == 0) wsum[wave] = v;
+  __syncthreads();
+  double r = 0.0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; ++w) r += wsum[w];
+  }
+  return r;  // valid in thread 0
+}
+
+template <typename T>
+__device__ __forceinline__ double sumsq_vec(const uint4& raw, double acc) {
+  constexpr int kPer = 16 / (int)sizeof(T);
+  const T* e = reinterpret_cast<const T*>(&raw);
+#pragma unroll
+  for (int i = 0; i < kPer; ++i) {
+    const double d = (double)to_f32<T>(e[i]);
+    acc = fma(d, d, acc);  // d*d is exact, so this is acc + d^2 rounded once
+  }
+  return acc;
+}
+
+// kVec: x is 16-byte aligned; lanes stream uint4s (four in flight per
+// iteration) and the first lanes of the grid take the < 16-byte tail.
+template <typename T, bool kVec>
+__global__ void sumsq_kernel(const T* __restrict__ x, unsigned long long n,
+                             double* __restrict__ partials) {
+  __shared__ double wsum[kBlock / kWave];
+  const unsigned long long tid =
+      (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long stride =
+      (unsigned long long)gridDim.x * blockDim.x;
+  double acc = 0.0;
+  if constexpr (kVec) {
+    constexpr int kPer = 16 / (int)sizeof(T);
+    const unsigned long long nvec = n / kPer;
+    const uint4* xv = reinterpret_cast<const uint4*>(x);
+    unsigned long long v = tid;
+    for (; v + 3ull * stride < nvec; v += 4ull * stride) {
+      const uint4 r0 = xv[v];
+      const uint4 r1 = xv[v + stride];
+      const uint4 r2 = xv[v + 2ull * stride];
+      const uint4 r3 = xv[v + 3ull * stride];
+      acc = sumsq_vec<T>(r0, acc);
+      acc = sumsq_vec<T>(r1, acc);
+      acc = sumsq_vec<T>(r2, acc);
+      acc = sumsq_vec<T>(r3, acc);
+    }
+    for (; v < nvec; v += stride) acc = sumsq_vec<T>(xv[v], acc);
+    const unsigned long long i = nvec * kPer + tid;  // tail: < kPer elements
+    if (i < n) {
+      const double d = (double)to_f32<T>(x[i]);
+      acc = fma(d, d, acc);
+    }
+  } else {
+    for (unsigned long long i = tid; i < n; i += stride) {
+      const double d = (double)to_f32<T>(x[i]);
+      acc = fma(d, d, acc);
+    }
+  }
+  const double r = sumsq_block_reduce(acc, wsum);
+  if (threadIdx.x == 0) partials[blockIdx.x] = r;
+}
+
+__global__ void sumsq_final_kernel(const double* __restrict__ partials,
+                                   int count, double* __restrict__ out) {
+  __shared__ double wsum[kBlock / kWave];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < count; i += kBlock) acc += partials[i];
+  const double r = sumsq_block_reduce(acc, wsum);
+  if (threadIdx.x == 0) out[0] = r;
 }
 
 // OutT = int32_t stores the raw ring sum (the accumulator between chunked
@@ -347,6 +543,156 @@ void secagg_mask_async(torch::Tensor x, torch::Tensor out, torch::Tensor keys,
   } else {
     TORCH_CHECK(false, "secagg_mask: unsupported dtype ", x.dtype());
   }
+}
+
+template <typename T>
+void secagg_launch_mask_noise(int words, int blocks, hipStream_t stream,
+                              const T* x, int32_t* out, unsigned long long n,
+                              unsigned long long blk0, uint32_t n0,
+                              uint32_t n1, float w, float scale,
+                              const SecaggKeys& k, const SecaggNoiseKey& nk,
+                              uint32_t step, bool vec_ok) {
+#define SECAGG_NOISE_CASE(W)                                                 \
+  case W:                                                                    \
+    hipLaunchKernelGGL((secagg_mask_noise_kernel<T, W>), dim3(blocks),       \
+                       dim3(kBlock), 0, stream, x, out, n, blk0, n0, n1, w,  \
+                       scale, k, nk, step, vec_ok);                          \
+    break;
+  switch (words) {
+    SECAGG_NOISE_CASE(1)
+    SECAGG_NOISE_CASE(2)
+    SECAGG_NOISE_CASE(4)
+    SECAGG_NOISE_CASE(8)
+    SECAGG_NOISE_CASE(16)
+    default:
+      TORCH_CHECK(false, "secagg_mask_noise: words must be 1, 2, 4, 8 or 16");
+  }
+#undef SECAGG_NOISE_CASE
+}
+
+// max_blocks = 0: the normal grid; > 0 caps it (drives the grid-stride loop
+// at a small n).
+void secagg_mask_noise_async(torch::Tensor x, torch::Tensor out,
+                             torch::Tensor keys, torch::Tensor signs,
+                             torch::Tensor noise_key, int64_t words,
+                             int64_t step, uint64_t round, int64_t offset,
+                             double weight, int64_t frac_bits,
+                             int64_t max_blocks) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
+              "secagg_mask_noise: x must be CUDA contiguous");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+                  out.dtype() == torch::kInt32 &&
+                  out.numel() == x.numel() && out.device() == x.device(),
+              "secagg_mask_noise: out must be a contiguous int32 tensor of "
+              "x's length on x's device");
+  TORCH_CHECK(x.dtype() == torch::kBFloat16 || x.dtype() == torch::kHalf ||
+                  x.dtype() == torch::kFloat,
+              "secagg_mask_noise: unsupported dtype ", x.dtype());
+  secagg_check_keys("secagg_mask_noise", keys, signs);
+  TORCH_CHECK(keys.size(0) <= kSecaggMaxKeys - 1,
+              "secagg_mask_noise: at most 15 peers");
+  TORCH_CHECK(!noise_key.is_cuda() && noise_key.dtype() == torch::kUInt8 &&
+                  noise_key.is_contiguous() && noise_key.dim() == 1 &&
+                  noise_key.size(0) == 32,
+              "secagg_mask_noise: noise_key must be a contiguous CPU "
+              "uint8[32] tensor");
+  TORCH_CHECK(words == 1 || words == 2 || words == 4 || words == 8 ||
+                  words == 16,
+              "secagg_mask_noise: words must be 1, 2, 4, 8 or 16");
+  TORCH_CHECK(step >= 1 && step <= kSecaggMaxNoiseStep,
+              "secagg_mask_noise: step must be in [1, 2^20]");
+  TORCH_CHECK(max_blocks >= 0, "secagg_mask_noise: max_blocks must be >= 0");
+  const unsigned long long n = x.numel();
+  secagg_check_range("secagg_mask_noise", n, offset, frac_bits);
+  // offset + n <= 2^36 holds, so the product below cannot overflow 64 bits.
+  TORCH_CHECK(((unsigned long long)offset + n) * (unsigned long long)words <=
+                  kSecaggMaxElements,
+              "secagg_mask_noise: (offset + n) * words exceeds 2^36 (the "
+              "noise stream's ChaCha20 counter would wrap)");
+  if (n == 0) return;
+  SecaggKeys k{};
+  secagg_fill_keys(k, keys, signs, 0, keys.size(0));
+  SecaggNoiseKey nk{};
+  const uint8_t* np = noise_key.data_ptr<uint8_t>();
+  for (int w = 0; w < 8; ++w) {
+    const uint8_t* p = np + w * 4;
+    nk.key[w] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) |
+                ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+  }
+  const bool vec_ok =
+      secagg_aligned16(x.data_ptr()) && secagg_aligned16(out.data_ptr());
+  const unsigned long long blk0 = (unsigned long long)offset / 16ull;
+  const uint32_t n0 = (uint32_t)(round & 0xffffffffull);
+  const uint32_t n1 = (uint32_t)(round >> 32);
+  const float w = (float)weight;
+  const float scale = (float)(1ull << frac_bits);
+  int blocks = secagg_grid((n + 15ull) / 16ull);
+  if (max_blocks > 0 && max_blocks < blocks) blocks = (int)max_blocks;
+  auto stream = at::hip::getCurrentHIPStream();
+  int32_t* o = out.data_ptr<int32_t>();
+  if (x.dtype() == torch::kBFloat16) {
+    secagg_launch_mask_noise<uint16_t>(
+        (int)words, blocks, stream,
+        reinterpret_cast<const uint16_t*>(x.data_ptr()), o, n, blk0, n0, n1,
+        w, scale, k, nk, (uint32_t)step, vec_ok);
+  } else if (x.dtype() == torch::kHalf) {
+    secagg_launch_mask_noise<__half>(
+        (int)words, blocks, stream,
+        reinterpret_cast<const __half*>(x.data_ptr()), o, n, blk0, n0, n1, w,
+        scale, k, nk, (uint32_t)step, vec_ok);
+  } else {
+    secagg_launch_mask_noise<float>((int)words, blocks, stream,
+                                    x.data_ptr<float>(), o, n, blk0, n0, n1,
+                                    w, scale, k, nk, (uint32_t)step, vec_ok);
+  }
+}
+
+// Enough blocks for 8 waves per SIMD on 256 CUs; one double per block.
+constexpr int kSumsqMaxBlocks = 2048;
+
+template <typename T>
+void sumsq_launch(const T* x, unsigned long long n, int blocks,
+                  double* partials, hipStream_t stream) {
+  if (secagg_aligned16(x)) {
+    hipLaunchKernelGGL((sumsq_kernel<T, true>), dim3(blocks), dim3(kBlock), 0,
+                       stream, x, n, partials);
+  } else {
+    hipLaunchKernelGGL((sumsq_kernel<T, false>), dim3(blocks), dim3(kBlock),
+                       0, stream, x, n, partials);
+  }
+}
+
+torch::Tensor sumsq_async(torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
+              "sumsq: x must be CUDA contiguous");
+  TORCH_CHECK(x.dtype() == torch::kBFloat16 || x.dtype() == torch::kHalf ||
+                  x.dtype() == torch::kFloat,
+              "sumsq: unsupported dtype ", x.dtype());
+  auto opts = torch::dtype(torch::kFloat64).device(x.device());
+  const unsigned long long n = x.numel();
+  if (n == 0) return torch::zeros({1}, opts);
+  auto out = torch::empty({1}, opts);
+  // one 16-byte load per lane per item; the scalar path just strides more
+  const unsigned long long per = 16ull / (unsigned long long)x.element_size();
+  const unsigned long long want = ((n + per - 1) / per + kBlock - 1) / kBlock;
+  const int blocks = (int)std::min<unsigned long long>(
+      (unsigned long long)kSumsqMaxBlocks, want);
+  auto partials = torch::empty({(long long)blocks}, opts);
+  auto stream = at::hip::getCurrentHIPStream();
+  double* pp = partials.data_ptr<double>();
+  if (x.dtype() == torch::kBFloat16) {
+    sumsq_launch<uint16_t>(reinterpret_cast<const uint16_t*>(x.data_ptr()), n,
+                           blocks, pp, stream);
+  } else if (x.dtype() == torch::kHalf) {
+    sumsq_launch<__half>(reinterpret_cast<const __half*>(x.data_ptr()), n,
+                         blocks, pp, stream);
+  } else {
+    sumsq_launch<float>(x.data_ptr<float>(), n, blocks, pp, stream);
+  }
+  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(kBlock), 0, stream,
+                     static_cast<const double*>(pp), blocks,
+                     out.data_ptr<double>());
+  return out;
 }
 
 template <typename OutT, int EPL>

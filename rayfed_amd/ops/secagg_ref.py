@@ -38,6 +38,38 @@ Aggregate
     mod 2^32; ``out[e] = cast(fl32(int32(S[e])) * 2^-frac_bits)``.  The
     int->fp32 conversion and the cast to fp32/bf16/fp16 are
     round-to-nearest-even.
+
+Differential privacy (optional; clip, then binomial noise before masking)
+
+Noise stream
+    ``NS(key, round, w)`` is word ``w mod 16`` of the ChaCha20 block with
+    the party's private 32-byte *noise key*, block counter ``w div 16`` and
+    nonce words ``(round & 0xffffffff, round >> 32, 1)``.  The third nonce
+    word separates it from every pair-mask keystream (which uses 0) even
+    if a key were reused.
+
+Binomial noise
+    Parameters ``words`` (W) in {1, 2, 4, 8, 16} - an element's words never
+    straddle a block - and ``step``, an int in [1, 2^20].  For element ``e``
+    of the logical flat vector
+    ``noise[e] = step * (sum_{t<W} popcount(NS(key, round, W*e + t)) - 16*W)``
+    mod 2^32: ``step * (Bin(32W, 1/2) - 16W)``, variance ``8*W*step^2`` in
+    fixed-point units, ``|noise[e]| <= 16*W*step``.  The counter never
+    wraps: ``offset % 16 == 0`` and ``(offset + n) * W <= 2^36`` are
+    validated.
+
+Mask with noise
+    ``y_i[e] = q_i[e] + noise_i[offset+e] + sum_{j != i} s(i,j) * KS(...)``
+    mod 2^32.  The noise rides in the ring sum: the aggregate is the
+    quantised sum plus the survivors' noises, exactly.  The caller must keep
+    ``|sum_i w_i x_i| + 16*W*step*contributors/2^frac_bits
+    < 2^(31 - frac_bits)``.
+
+Sum of squares (for L2 clipping)
+    ``sum_e float64(x[e])^2`` accumulated in float64.  Every square of an
+    fp32/bf16/fp16 value is exact in float64; only the order of the
+    additions is unspecified, so two conforming results differ by at most
+    ``n * 2^-52`` relative.
 """
 from __future__ import annotations
 
@@ -48,6 +80,9 @@ import numpy as np
 MAX_PARTIES = 16
 MAX_FRAC_BITS = 30
 MAX_ELEMENTS = 1 << 36  # 2^32 blocks of 16 words: the counter never wraps
+NOISE_WORDS = (1, 2, 4, 8, 16)  # keystream words per element
+MAX_NOISE_STEP = 1 << 20
+NOISE_NONCE_WORD = 1  # third nonce word of the noise stream (masks use 0)
 _CONSTANTS = (0x61707865, 0x3320646E, 0x79622D32, 0x6B206574)
 
 
@@ -218,3 +253,69 @@ def aggregate_ref(masked: Sequence[np.ndarray], corr_keys: Sequence[bytes],
     s = ring_sum_ref(masked, corr_keys, corr_signs, round, offset)
     f = s.astype(np.float32) * np.float32(2.0 ** -frac_bits)
     return cast_ref(f, out_dtype)
+
+
+# ------------------------------------------------- binomial noise (DP)
+def check_noise(words: int, step: int) -> None:
+    if isinstance(words, bool) or not isinstance(words, int) \
+            or words not in NOISE_WORDS:
+        raise ValueError(f"noise words must be one of {NOISE_WORDS}")
+    if isinstance(step, bool) or not isinstance(step, int) \
+            or not 1 <= step <= MAX_NOISE_STEP:
+        raise ValueError("noise step must be an int in [1, 2^20]")
+
+
+def check_noise_range(offset: int, n: int, words: int) -> None:
+    """The noise rule: ``words`` keystream words per element."""
+    if offset < 0 or n < 0:
+        raise ValueError("offset and length must be non-negative")
+    if offset % 16 != 0:
+        raise ValueError("secagg offset must be a multiple of 16")
+    if (offset + n) * words > MAX_ELEMENTS:
+        raise ValueError(
+            "(offset + n) * words exceeds 2^36: the ChaCha20 block counter "
+            "of the noise stream would wrap")
+
+
+def _popcount32(v: np.ndarray) -> np.ndarray:
+    """Bit count of every uint32 (SWAR; no numpy-version dependence)."""
+    v = v - ((v >> np.uint32(1)) & np.uint32(0x55555555))
+    v = (v & np.uint32(0x33333333)) + ((v >> np.uint32(2))
+                                       & np.uint32(0x33333333))
+    v = (v + (v >> np.uint32(4))) & np.uint32(0x0F0F0F0F)
+    return (v * np.uint32(0x01010101)) >> np.uint32(24)
+
+
+def binomial_noise(key: bytes, round: int, offset: int, n: int, words: int,
+                   step: int) -> np.ndarray:
+    """``noise[offset+e]`` for ``e in [0, n)`` as ``uint32[n]`` (mod 2^32)."""
+    if not isinstance(key, (bytes, bytearray)) or len(key) != 32:
+        raise ValueError("a noise key must be exactly 32 bytes")
+    check_round(round)
+    check_noise(words, step)
+    check_noise_range(offset, n, words)
+    nblocks = (n * words + 15) // 16
+    nonce = (round & 0xFFFFFFFF, round >> 32, NOISE_NONCE_WORD)
+    ns = chacha20_blocks(key, offset // 16 * words, nonce, nblocks)
+    bits = _popcount32(ns.reshape(-1)[:n * words]).reshape(n, words)
+    centred = bits.sum(axis=1, dtype=np.int64) - 16 * words
+    return (centred * step).astype(np.uint32)  # two's complement wrap
+
+
+def mask_noise_ref(x, weight: float, frac_bits: int, keys: Sequence[bytes],
+                   signs: Sequence[int], round: int, offset: int,
+                   noise_key: bytes, words: int, step: int) -> np.ndarray:
+    """``mask_ref(...) + binomial_noise(noise_key, ...)`` mod 2^32 as
+    ``int32``."""
+    x = np.asarray(x, dtype=np.float32).reshape(-1)
+    noise = binomial_noise(noise_key, round, offset, x.size, words, step)
+    y = mask_ref(x, weight, frac_bits, keys, signs, round, offset)
+    return (y.view(np.uint32) + noise).view(np.int32)
+
+
+def sum_squares_ref(x) -> float:
+    """Float64 sum of the squares of ``x``'s values widened exactly to
+    float64 (NaN / Inf propagate; 0.0 for an empty array)."""
+    v = np.asarray(x).astype(np.float64).reshape(-1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return float(np.sum(v * v))

@@ -15,7 +15,13 @@ On CUDA tensors masking and aggregation are the HIP kernels in
 specification.  Both produce identical bits.
 
 The caller must keep ``|sum_i w_i x_i| < 2^(31 - frac_bits)`` for every
-element, or the ring sum wraps.  Key agreement is out of scope: a session
+element, or the ring sum wraps.  With differential-privacy noise
+(``mask(..., noise=BinomialNoise(...))``, see :mod:`rayfed_amd.parallel.dp`)
+the rule is ``|sum_i w_i x_i| + noise.max_abs(frac_bits, contributors)
+< 2^(31 - frac_bits)``.  The noise rides in the ring sum, so ``aggregate``
+is unchanged; a dropped party's noise is absent from the sum, so each party
+should size its share for the smallest number of survivors it is willing to
+accept.  Key agreement is out of scope: a session
 takes a ``{peer: key}`` mapping.  :func:`derive_pair_key` /
 :meth:`SecAggSession.from_shared_secret` derive pair keys from one secret
 known to all parties — a convenience for tests and demos, NOT a key
@@ -30,6 +36,7 @@ import numpy as np
 import torch
 
 from rayfed_amd.ops import secagg_ref
+from rayfed_amd.parallel.dp import BinomialNoise
 
 __all__ = ["SecAggSession", "aggregate", "derive_pair_key"]
 
@@ -137,17 +144,27 @@ class SecAggSession:
         return self._frac_bits
 
     def mask(self, x: torch.Tensor, round: int, weight: float = 1.0,
-             offset: int = 0, out: Optional[torch.Tensor] = None
-             ) -> torch.Tensor:
+             offset: int = 0, out: Optional[torch.Tensor] = None,
+             noise: Optional[BinomialNoise] = None) -> torch.Tensor:
         """Quantise ``weight * x`` and add this party's pairwise masks for
         ``round``; returns an int32 tensor of ``x``'s shape.  ``offset`` is
         the element index of ``x[0]`` in the logical flat vector (multiple
-        of 16), so bucket or chunk views can be masked independently."""
+        of 16), so bucket or chunk views can be masked independently.
+
+        ``noise`` adds this party's binomial noise (differential privacy,
+        see :mod:`rayfed_amd.parallel.dp`) to the quantised update before
+        the masks, in the same pass; ``(offset + n) * noise.words <= 2^36``
+        must then hold.  ``None`` is the plain path, bit for bit."""
         xf = _flat(x, "x")
         if xf.dtype not in _IN_DTYPES:
             raise ValueError(f"unsupported dtype {x.dtype}")
         secagg_ref.check_round(round)
-        secagg_ref.check_range(offset, xf.numel())
+        if noise is None:
+            secagg_ref.check_range(offset, xf.numel())
+        elif not isinstance(noise, BinomialNoise):
+            raise ValueError("noise must be a BinomialNoise or None")
+        else:
+            secagg_ref.check_noise_range(offset, xf.numel(), noise.words)
         if out is None:
             out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
         of = _flat(out, "out")
@@ -159,13 +176,28 @@ class SecAggSession:
             from rayfed_amd.ops import _hip_loader
 
             with torch.cuda.device(xf.device):
-                _hip_loader.load().secagg_mask_async(
-                    xf, of, self._key_t, self._sign_t, round, offset,
-                    float(weight), self._frac_bits)
+                if noise is None:
+                    _hip_loader.load().secagg_mask_async(
+                        xf, of, self._key_t, self._sign_t, round, offset,
+                        float(weight), self._frac_bits)
+                else:
+                    nk = torch.frombuffer(bytearray(noise.key),
+                                          dtype=torch.uint8)
+                    _hip_loader.load().secagg_mask_noise_async(
+                        xf, of, self._key_t, self._sign_t, nk, noise.words,
+                        noise.step, round, offset, float(weight),
+                        self._frac_bits)
             return out
-        y = secagg_ref.mask_ref(
-            xf.float().numpy(), float(weight), self._frac_bits,
-            [self._keys[p] for p in self._peers], self._signs, round, offset)
+        keys = [self._keys[p] for p in self._peers]
+        if noise is None:
+            y = secagg_ref.mask_ref(
+                xf.float().numpy(), float(weight), self._frac_bits, keys,
+                self._signs, round, offset)
+        else:
+            y = secagg_ref.mask_noise_ref(
+                xf.float().numpy(), float(weight), self._frac_bits, keys,
+                self._signs, round, offset, noise.key, noise.words,
+                noise.step)
         of.copy_(torch.from_numpy(y))
         return out
 
