@@ -90,19 +90,44 @@ __device__ __forceinline__ void load_crc_shared(CrcShared& sh,
   __syncthreads();
 }
 
-// xor-reduce `v` across the block, atomically xor into *out from one lane.
-__device__ __forceinline__ void block_xor_out(uint32_t v, uint32_t* out,
-                                              uint32_t* lds_scratch) {
+// xor-reduce `v` (a 32- or 64-bit word) across the block, atomically xor
+// into *out from one lane.
+template <typename W>
+__device__ __forceinline__ void block_xor_out(W v, W* out, W* lds_scratch) {
 #pragma unroll
   for (int off = kWave / 2; off > 0; off >>= 1) v ^= __shfl_down(v, off, kWave);
   const int wid = threadIdx.x / kWave;
   if ((threadIdx.x & (kWave - 1)) == 0) lds_scratch[wid] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
-    uint32_t acc = 0;
+    W acc = 0;
     for (int w = 0; w < (int)(blockDim.x / kWave); ++w) acc ^= lds_scratch[w];
     if (acc) atomicXor(out, acc);
   }
+}
+
+// `crc` shifted past k whole slices (binary powers of the slice matrix).
+__device__ __forceinline__ uint32_t crc_shift_slices(const CrcShared& sh,
+                                                     uint32_t crc,
+                                                     uint32_t k) {
+  int j = 0;
+  while (k) {
+    if (k & 1u) crc = gf2_apply(&sh.pows[j * 32], crc);
+    k >>= 1;
+    ++j;
+  }
+  return crc;
+}
+
+// The two block reductions that end a CRC kernel: out[0] ^= the full-slice
+// terms, out[1] ^= the tail term.
+__device__ __forceinline__ void crc_block_out(uint32_t contrib_full,
+                                              uint32_t contrib_tail,
+                                              uint32_t* out,
+                                              uint32_t* lds_scratch) {
+  block_xor_out(contrib_full, &out[0], lds_scratch);
+  __syncthreads();
+  block_xor_out(contrib_tail, &out[1], lds_scratch);
 }
 
 // ---------------------------------------------------------------------------
@@ -171,19 +196,10 @@ __global__ void crc32_kernel(const uint8_t* __restrict__ data,
     if (t == T - 1) {
       contrib_tail = crc;
     } else {
-      uint32_t k = T - 2 - t;
-      int j = 0;
-      while (k) {
-        if (k & 1u) crc = gf2_apply(&sh.pows[j * 32], crc);
-        k >>= 1;
-        ++j;
-      }
-      contrib_full = crc;
+      contrib_full = crc_shift_slices(sh, crc, T - 2 - t);
     }
   }
-  block_xor_out(contrib_full, &out[0], lds_scratch);
-  __syncthreads();
-  block_xor_out(contrib_tail, &out[1], lds_scratch);
+  crc_block_out(contrib_full, contrib_tail, out, lds_scratch);
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) {
@@ -234,20 +250,30 @@ __device__ __forceinline__ unsigned long long fmix64(unsigned long long h) {
   return h;
 }
 
-__device__ __forceinline__ void block_xor_out64(unsigned long long v,
-                                                unsigned long long* out,
-                                                unsigned long long* lds) {
+// The pieces every hash64-mapped kernel shares: the four lane accumulators'
+// start values, their fold into the lane's term, and lane 0's terms for the
+// tail word and the length.
+__device__ __forceinline__ void hash64_init(unsigned long long h[4],
+                                            uint32_t lane) {
 #pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1)
-    v ^= __shfl_down(v, off, kWave);
-  const int wid = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) lds[wid] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long acc = 0;
-    for (int w = 0; w < (int)(blockDim.x / kWave); ++w) acc ^= lds[w];
-    if (acc) atomicXor(out, acc);
-  }
+  for (int k = 0; k < 4; ++k)
+    h[k] = (kFnvOff ^ (unsigned long long)(lane * 4u + k)) * kFnvP;
+}
+
+__device__ __forceinline__ unsigned long long hash64_fold(
+    const unsigned long long h[4]) {
+  return fmix64(
+      ((((h[0] * kFnvP ^ h[1]) * kFnvP ^ h[2]) * kFnvP ^ h[3]) * kFnvP));
+}
+
+__device__ __forceinline__ unsigned long long hash64_tail_term(
+    unsigned long long tw) {
+  return fmix64((kFnvOff ^ tw) * kFnvP);
+}
+
+__device__ __forceinline__ unsigned long long hash64_len_term(
+    unsigned long long nbytes) {
+  return fmix64((nbytes * kFnvP) ^ kFnvOff);
 }
 
 template <bool kPack>
@@ -263,9 +289,7 @@ __global__ void hash64_kernel(const unsigned long long* __restrict__ words,
   const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;  // < kHashLanes
   const unsigned long long slots = 4ull * kHashLanes;
   unsigned long long h[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    h[k] = (kFnvOff ^ (unsigned long long)(lane * 4u + k)) * kFnvP;
+  hash64_init(h, lane);
   // Iteration j: lane reads words j*slots + lane*4 + k — consecutive lanes
   // read consecutive 32-byte chunks (fully coalesced); 4 independent
   // accumulators hide the multiply latency.  kPack fuses the staging copy
@@ -292,9 +316,7 @@ __global__ void hash64_kernel(const unsigned long long* __restrict__ words,
       }
     }
   }
-  unsigned long long hl =
-      ((((h[0] * kFnvP ^ h[1]) * kFnvP ^ h[2]) * kFnvP ^ h[3]) * kFnvP);
-  unsigned long long v = fmix64(hl);
+  unsigned long long v = hash64_fold(h);
   if (lane == 0) {
     if (tail_len) {
       unsigned long long tw = 0;
@@ -302,11 +324,11 @@ __global__ void hash64_kernel(const unsigned long long* __restrict__ words,
         tw |= (unsigned long long)tail[i] << (8 * i);
         if (kPack) dst_tail[i] = tail[i];
       }
-      v ^= fmix64((kFnvOff ^ tw) * kFnvP);
+      v ^= hash64_tail_term(tw);
     }
-    v ^= fmix64((nbytes * kFnvP) ^ kFnvOff);
+    v ^= hash64_len_term(nbytes);
   }
-  block_xor_out64(v, out, lds);
+  block_xor_out(v, out, lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -333,9 +355,7 @@ __global__ void fedavg_combine_hash_kernel(
   const unsigned long long* lw =
       reinterpret_cast<const unsigned long long*>(local);
   unsigned long long h[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    h[k] = (kFnvOff ^ (unsigned long long)(lane * 4u + k)) * kFnvP;
+  hash64_init(h, lane);
   for (unsigned long long base = (unsigned long long)lane * 4ull;
        base < n_words; base += slots) {
     if (base + 4 <= n_words) {
@@ -376,15 +396,13 @@ __global__ void fedavg_combine_hash_kernel(
       }
     }
   }
-  unsigned long long hl =
-      ((((h[0] * kFnvP ^ h[1]) * kFnvP ^ h[2]) * kFnvP ^ h[3]) * kFnvP);
-  unsigned long long v = fmix64(hl);
+  unsigned long long v = hash64_fold(h);
   if (lane == 0) {
     if (tail_len) {
       unsigned long long tw = 0;
       for (uint32_t i = 0; i < tail_len; ++i)
         tw |= (unsigned long long)peer_tail[i] << (8 * i);
-      v ^= fmix64((kFnvOff ^ tw) * kFnvP);
+      v ^= hash64_tail_term(tw);
       // Combine the tail elements too (bf16 => tail_len is even).
       const unsigned long long e0 = n_words * 4;
       for (uint32_t e = 0; e < tail_len / 2; ++e) {
@@ -394,9 +412,9 @@ __global__ void fedavg_combine_hash_kernel(
         out[e0 + e] = f32_to_bf16(fmaf(wa, l, wb * p));
       }
     }
-    v ^= fmix64((nbytes * kFnvP) ^ kFnvOff);
+    v ^= hash64_len_term(nbytes);
   }
-  block_xor_out64(v, hash_out, lds);
+  block_xor_out(v, hash_out, lds);
 }
 
 struct TailParam {
@@ -432,6 +450,19 @@ __device__ __forceinline__ float fp8_to_f32(uint8_t b) {
   __hip_fp8_e4m3 v;
   v.__x = b;
   return (float)v;
+}
+
+// 8 fp8 bytes (one u64 word) -> 8 bf16 in element order (one 16-byte store).
+__device__ __forceinline__ uint4 bf16x8_from_fp8x8(unsigned long long w) {
+  uint32_t parts[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    parts[e] =
+        (uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(w >> (16 * e)))) |
+        ((uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(w >> (16 * e + 8))))
+         << 16);
+  }
+  return make_uint4(parts[0], parts[1], parts[2], parts[3]);
 }
 
 // src: bf16 elements; dst: fp8 bytes.  Thread t produces kSubLen output
@@ -483,19 +514,10 @@ __global__ void pack_fp8_kernel(const uint16_t* __restrict__ src,
     if (t == T - 1) {
       contrib_tail = crc;
     } else {
-      uint32_t k = T - 2 - t;
-      int j = 0;
-      while (k) {
-        if (k & 1u) crc = gf2_apply(&sh.pows[j * 32], crc);
-        k >>= 1;
-        ++j;
-      }
-      contrib_full = crc;
+      contrib_full = crc_shift_slices(sh, crc, T - 2 - t);
     }
   }
-  block_xor_out(contrib_full, &out[0], lds_scratch);
-  __syncthreads();
-  block_xor_out(contrib_tail, &out[1], lds_scratch);
+  crc_block_out(contrib_full, contrib_tail, out, lds_scratch);
 }
 
 // fp8 wire cast fused with the hash64 slot mapping over the PRODUCED fp8
@@ -511,9 +533,7 @@ __global__ void pack_fp8_hash64_kernel(const uint16_t* __restrict__ src,
   const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long slots = 4ull * kHashLanes;
   unsigned long long h[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    h[k] = (kFnvOff ^ (unsigned long long)(lane * 4u + k)) * kFnvP;
+  hash64_init(h, lane);
   for (unsigned long long base = (unsigned long long)lane * 4ull;
        base < n_words; base += slots) {
     const int cnt = (int)((base + 4 <= n_words) ? 4 : (n_words - base));
@@ -535,9 +555,7 @@ __global__ void pack_fp8_hash64_kernel(const uint16_t* __restrict__ src,
       dst[i] = w;
     }
   }
-  unsigned long long hl =
-      ((((h[0] * kFnvP ^ h[1]) * kFnvP ^ h[2]) * kFnvP ^ h[3]) * kFnvP);
-  unsigned long long v = fmix64(hl);
+  unsigned long long v = hash64_fold(h);
   if (lane == 0) {
     if (tail_elems) {
       unsigned long long tw = 0;
@@ -547,11 +565,11 @@ __global__ void pack_fp8_hash64_kernel(const uint16_t* __restrict__ src,
         dtail[e] = b;
         tw |= (unsigned long long)b << (8 * e);
       }
-      v ^= fmix64((kFnvOff ^ tw) * kFnvP);
+      v ^= hash64_tail_term(tw);
     }
-    v ^= fmix64((nbytes * kFnvP) ^ kFnvOff);
+    v ^= hash64_len_term(nbytes);
   }
-  block_xor_out64(v, out, lds);
+  block_xor_out(v, out, lds);
 }
 
 // Inverse: fp8 -> bf16 expand fused with the hash64 of the INPUT fp8 bytes
@@ -565,9 +583,7 @@ __global__ void unpack_fp8_hash64_kernel(
   const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long slots = 4ull * kHashLanes;
   unsigned long long h[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    h[k] = (kFnvOff ^ (unsigned long long)(lane * 4u + k)) * kFnvP;
+  hash64_init(h, lane);
   for (unsigned long long base = (unsigned long long)lane * 4ull;
        base < n_words; base += slots) {
     const int cnt = (int)((base + 4 <= n_words) ? 4 : (n_words - base));
@@ -575,25 +591,10 @@ __global__ void unpack_fp8_hash64_kernel(
       const unsigned long long i = base + k;
       const unsigned long long w = src[i];
       h[k] = (h[k] ^ w) * kFnvP;
-      uint4 o;
-      uint32_t parts[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        parts[e] =
-            (uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(w >> (16 * e)))) |
-            ((uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(w >> (16 * e + 8))))
-             << 16);
-      }
-      o.x = parts[0];
-      o.y = parts[1];
-      o.z = parts[2];
-      o.w = parts[3];
-      *reinterpret_cast<uint4*>(dst + i * 8) = o;
+      *reinterpret_cast<uint4*>(dst + i * 8) = bf16x8_from_fp8x8(w);
     }
   }
-  unsigned long long hl =
-      ((((h[0] * kFnvP ^ h[1]) * kFnvP ^ h[2]) * kFnvP ^ h[3]) * kFnvP);
-  unsigned long long v = fmix64(hl);
+  unsigned long long v = hash64_fold(h);
   if (lane == 0) {
     if (tail_elems) {
       unsigned long long tw = 0;
@@ -602,11 +603,11 @@ __global__ void unpack_fp8_hash64_kernel(
         tw |= (unsigned long long)stail[e] << (8 * e);
         dst[n_words * 8 + e] = f32_to_bf16(fp8_to_f32(stail[e]));
       }
-      v ^= fmix64((kFnvOff ^ tw) * kFnvP);
+      v ^= hash64_tail_term(tw);
     }
-    v ^= fmix64((nbytes * kFnvP) ^ kFnvOff);
+    v ^= hash64_len_term(nbytes);
   }
-  block_xor_out64(v, out, lds);
+  block_xor_out(v, out, lds);
 }
 
 // kVec: src is 8-byte and dst 16-byte aligned (decided on the host).
@@ -621,16 +622,8 @@ __global__ void unpack_fp8_kernel(const uint8_t* __restrict__ src,
        base < n_elems; base += stride) {
     if (kVec && base + 8 <= n_elems) {
       const uint2 v = *reinterpret_cast<const uint2*>(src + base);
-      uint4 o;
-      o.x = (uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.x))) |
-            ((uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.x >> 8))) << 16);
-      o.y = (uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.x >> 16))) |
-            ((uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.x >> 24))) << 16);
-      o.z = (uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.y))) |
-            ((uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.y >> 8))) << 16);
-      o.w = (uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.y >> 16))) |
-            ((uint32_t)f32_to_bf16(fp8_to_f32((uint8_t)(v.y >> 24))) << 16);
-      *reinterpret_cast<uint4*>(dst + base) = o;
+      *reinterpret_cast<uint4*>(dst + base) =
+          bf16x8_from_fp8x8(v.x | ((unsigned long long)v.y << 32));
     } else {
       const unsigned long long end =
           base + 8 <= n_elems ? base + 8 : n_elems;
@@ -857,83 +850,132 @@ inline bool aligned_to(const void* p, uintptr_t bytes) {
   return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
 }
 
-inline uint32_t n_threads_for(unsigned long long nbytes) {
-  return (uint32_t)((nbytes + kSubLen - 1) / kSubLen);
+// The recurring argument check; each caller raises its own message.
+inline bool cuda_contiguous(const torch::Tensor& t, at::ScalarType dtype) {
+  return t.is_cuda() && t.dtype() == dtype && t.is_contiguous();
+}
+
+// Kernel element types as bits, so that a call site names the ones it has
+// kernels for.
+constexpr unsigned kBf16 = 1u, kF16 = 2u, kF32 = 4u;
+constexpr unsigned kAnyFloat = kBf16 | kF16 | kF32;
+
+inline unsigned elem_bit(const torch::Tensor& t) {
+  return t.dtype() == torch::kBFloat16 ? kBf16
+         : t.dtype() == torch::kHalf   ? kF16
+         : t.dtype() == torch::kFloat  ? kF32
+                                       : 0u;
+}
+
+// Calls f(T{}) with the kernel element type of t's dtype: uint16_t for bf16,
+// __half, float.  A dtype outside kAllowed raises `msg` followed by the dtype,
+// and f is instantiated for the allowed types only.
+template <unsigned kAllowed, typename F>
+void dispatch_elem(const torch::Tensor& t, const char* msg, F&& f) {
+  const unsigned bit = elem_bit(t) & kAllowed;
+  TORCH_CHECK(bit, msg, t.dtype());
+  if constexpr ((kAllowed & kBf16) != 0) {
+    if (bit == kBf16) return f(uint16_t{});
+  }
+  if constexpr ((kAllowed & kF16) != 0) {
+    if (bit == kF16) return f(__half{});
+  }
+  if constexpr ((kAllowed & kF32) != 0) {
+    if (bit == kF32) return f(float{});
+  }
+}
+
+template <typename T>
+T* elem_ptr(const torch::Tensor& t) {
+  return reinterpret_cast<T*>(t.data_ptr());
+}
+
+// Launch shared by the CRC kernels (one thread per kSubLen output bytes) and
+// the finalize kernel behind them: int32[3] on src's device, out[2] = CRC32
+// of the src.numel() bytes the kernel reads or produces.
+template <typename SrcT>
+torch::Tensor crc_launch(void (*kernel)(const SrcT*, uint8_t*,
+                                        unsigned long long, uint32_t,
+                                        const uint32_t*, const uint32_t*,
+                                        const uint32_t*, uint32_t*),
+                         const torch::Tensor& src, uint8_t* dst) {
+  const unsigned long long n = src.numel();
+  auto out = torch::zeros(
+      {3}, torch::dtype(torch::kInt32).device(src.device()));
+  if (n == 0) return out;  // crc32("") == 0 — out[2] already 0
+  auto& consts = get_device_consts();
+  const uint32_t T = (uint32_t)((n + kSubLen - 1) / kSubLen);  // threads
+  const uint32_t blocks = (T + kBlock - 1) / kBlock;
+  auto stream = at::hip::getCurrentHIPStream();
+  uint32_t* o = reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>());
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream,
+                     elem_ptr<const SrcT>(src), dst, n, T, consts.tables,
+                     consts.pows, consts.halfmat, o);
+  hipLaunchKernelGGL(crc_finalize_kernel, dim3(1), dim3(kWave), 0, stream, o,
+                     make_tail_param(n, T));
+  return out;
+}
+
+// Launch shared by the hash64-mapped kernels: the zeroed int64[1] result on
+// `dev`, the split of nbytes into u64 words and a tail, and the fixed grid
+// the slot mapping rests on.  launch(grid, stream, n_words, tail, out) starts
+// the kernel.
+template <typename F>
+torch::Tensor hash64_launch(const torch::Device& dev,
+                            unsigned long long nbytes, F&& launch) {
+  auto out = torch::zeros({1}, torch::dtype(torch::kInt64).device(dev));
+  launch(dim3(kHashLanes / kBlock), at::hip::getCurrentHIPStream(),
+         nbytes / 8, (uint32_t)(nbytes % 8),
+         reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>()));
+  return out;
 }
 
 // ---------------------------------------------------------------------------
 // torch bindings
 // ---------------------------------------------------------------------------
 torch::Tensor crc32_async(torch::Tensor bytes) {
-  TORCH_CHECK(bytes.is_cuda() && bytes.dtype() == torch::kUInt8 &&
-                  bytes.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(bytes, torch::kUInt8),
               "crc32 expects a contiguous CUDA uint8 tensor");
-  const unsigned long long n = bytes.numel();
-  auto out = torch::zeros(
-      {3}, torch::dtype(torch::kInt32).device(bytes.device()));
-  if (n == 0) return out;  // crc32("") == 0 — out[2] already 0
-  auto& consts = get_device_consts();
-  const uint32_t T = n_threads_for(n);
-  const uint32_t blocks = (T + kBlock - 1) / kBlock;
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(crc32_kernel<false>, dim3(blocks), dim3(kBlock), 0,
-                     stream, bytes.data_ptr<uint8_t>(), nullptr, n, T,
-                     consts.tables, consts.pows, consts.halfmat,
-                     reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()));
-  hipLaunchKernelGGL(crc_finalize_kernel, dim3(1), dim3(kWave), 0, stream,
-                     reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()),
-                     make_tail_param(n, T));
-  return out;
+  return crc_launch(crc32_kernel<false>, bytes, nullptr);
 }
 
 torch::Tensor hash64_async(torch::Tensor bytes) {
-  TORCH_CHECK(bytes.is_cuda() && bytes.dtype() == torch::kUInt8 &&
-                  bytes.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(bytes, torch::kUInt8),
               "hash64 expects a contiguous CUDA uint8 tensor");
   const unsigned long long n = bytes.numel();
-  auto out = torch::zeros(
-      {1}, torch::dtype(torch::kInt64).device(bytes.device()));
   const uint8_t* p = bytes.data_ptr<uint8_t>();
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 7u) == 0,
-              "hash64 requires 8-byte-aligned data");
-  const unsigned long long n_words = n / 8;
-  const uint32_t tail_len = (uint32_t)(n % 8);
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(hash64_kernel<false>, dim3(kHashLanes / kBlock),
-                     dim3(kBlock), 0, stream,
-                     reinterpret_cast<const unsigned long long*>(p), nullptr,
-                     n_words, p + n_words * 8, nullptr, tail_len, n,
-                     reinterpret_cast<unsigned long long*>(
-                         out.data_ptr<int64_t>()));
-  return out;
+  TORCH_CHECK(aligned_to(p, 8), "hash64 requires 8-byte-aligned data");
+  return hash64_launch(
+      bytes.device(), n,
+      [&](dim3 grid, hipStream_t stream, unsigned long long n_words,
+          uint32_t tail_len, unsigned long long* out) {
+        hipLaunchKernelGGL(hash64_kernel<false>, grid, dim3(kBlock), 0, stream,
+                           reinterpret_cast<const unsigned long long*>(p),
+                           nullptr, n_words, p + n_words * 8, nullptr,
+                           tail_len, n, out);
+      });
 }
 
 torch::Tensor pack_hash64_async(torch::Tensor src, torch::Tensor dst) {
-  TORCH_CHECK(src.is_cuda() && src.dtype() == torch::kUInt8 &&
-                  src.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(src, torch::kUInt8),
               "pack_hash64 expects contiguous CUDA uint8 src");
-  TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kUInt8 &&
-                  dst.is_contiguous() && dst.numel() >= src.numel(),
+  TORCH_CHECK(cuda_contiguous(dst, torch::kUInt8) &&
+                  dst.numel() >= src.numel(),
               "pack_hash64 dst too small");
   const unsigned long long n = src.numel();
-  auto out = torch::zeros(
-      {1}, torch::dtype(torch::kInt64).device(src.device()));
   const uint8_t* p = src.data_ptr<uint8_t>();
   uint8_t* q = dst.data_ptr<uint8_t>();
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 7u) == 0 &&
-                  (reinterpret_cast<uintptr_t>(q) & 7u) == 0,
+  TORCH_CHECK(aligned_to(p, 8) && aligned_to(q, 8),
               "pack_hash64 requires 8-byte alignment");
-  const unsigned long long n_words = n / 8;
-  const uint32_t tail_len = (uint32_t)(n % 8);
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(hash64_kernel<true>, dim3(kHashLanes / kBlock),
-                     dim3(kBlock), 0, stream,
-                     reinterpret_cast<const unsigned long long*>(p),
-                     reinterpret_cast<unsigned long long*>(q), n_words,
-                     p + n_words * 8, q + n_words * 8, tail_len, n,
-                     reinterpret_cast<unsigned long long*>(
-                         out.data_ptr<int64_t>()));
-  return out;
+  return hash64_launch(
+      src.device(), n,
+      [&](dim3 grid, hipStream_t stream, unsigned long long n_words,
+          uint32_t tail_len, unsigned long long* out) {
+        hipLaunchKernelGGL(hash64_kernel<true>, grid, dim3(kBlock), 0, stream,
+                           reinterpret_cast<const unsigned long long*>(p),
+                           reinterpret_cast<unsigned long long*>(q), n_words,
+                           p + n_words * 8, q + n_words * 8, tail_len, n, out);
+      });
 }
 
 int64_t crc32_sync(torch::Tensor bytes) {
@@ -942,124 +984,75 @@ int64_t crc32_sync(torch::Tensor bytes) {
 }
 
 torch::Tensor pack_crc_async(torch::Tensor src, torch::Tensor dst) {
-  TORCH_CHECK(src.is_cuda() && src.dtype() == torch::kUInt8 &&
-                  src.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(src, torch::kUInt8),
               "pack_crc expects contiguous CUDA uint8 src");
-  TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kUInt8 &&
-                  dst.is_contiguous() && dst.numel() >= src.numel(),
+  TORCH_CHECK(cuda_contiguous(dst, torch::kUInt8) &&
+                  dst.numel() >= src.numel(),
               "pack_crc dst too small");
   // The kernel picks 16-byte loads AND stores from src's alignment alone.
   TORCH_CHECK(!aligned_to(src.data_ptr(), 16) || aligned_to(dst.data_ptr(), 16),
               "pack_crc: dst must be 16-byte aligned when src is");
-  const unsigned long long n = src.numel();
-  auto out = torch::zeros(
-      {3}, torch::dtype(torch::kInt32).device(src.device()));
-  if (n == 0) return out;
-  auto& consts = get_device_consts();
-  const uint32_t T = n_threads_for(n);
-  const uint32_t blocks = (T + kBlock - 1) / kBlock;
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(crc32_kernel<true>, dim3(blocks), dim3(kBlock), 0,
-                     stream, src.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(),
-                     n, T, consts.tables, consts.pows, consts.halfmat,
-                     reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()));
-  hipLaunchKernelGGL(crc_finalize_kernel, dim3(1), dim3(kWave), 0, stream,
-                     reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()),
-                     make_tail_param(n, T));
-  return out;
+  return crc_launch(crc32_kernel<true>, src, dst.data_ptr<uint8_t>());
 }
 
 torch::Tensor pack_fp8_async(torch::Tensor src, torch::Tensor dst) {
-  TORCH_CHECK(src.is_cuda() && src.dtype() == torch::kBFloat16 &&
-                  src.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(src, torch::kBFloat16),
               "pack_fp8 expects contiguous CUDA bf16 src");
-  TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kUInt8 &&
-                  dst.is_contiguous() && dst.numel() >= src.numel(),
+  TORCH_CHECK(cuda_contiguous(dst, torch::kUInt8) &&
+                  dst.numel() >= src.numel(),
               "pack_fp8 dst too small");
-  const unsigned long long n = src.numel();
-  auto out = torch::zeros(
-      {3}, torch::dtype(torch::kInt32).device(src.device()));
-  if (n == 0) return out;
-  auto& consts = get_device_consts();
-  const uint32_t T = n_threads_for(n);
-  const uint32_t blocks = (T + kBlock - 1) / kBlock;
-  auto stream = at::hip::getCurrentHIPStream();
   // uint4 loads of src / uint2 stores of dst need 16 / 8-byte alignment;
   // views at odd element offsets take the scalar instantiation.
   const bool vec =
       aligned_to(src.data_ptr(), 16) && aligned_to(dst.data_ptr(), 8);
-  hipLaunchKernelGGL(vec ? pack_fp8_kernel<true> : pack_fp8_kernel<false>,
-                     dim3(blocks), dim3(kBlock), 0, stream,
-                     reinterpret_cast<const uint16_t*>(src.data_ptr()),
-                     dst.data_ptr<uint8_t>(), n, T, consts.tables, consts.pows,
-                     consts.halfmat,
-                     reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()));
-  hipLaunchKernelGGL(crc_finalize_kernel, dim3(1), dim3(kWave), 0, stream,
-                     reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()),
-                     make_tail_param(n, T));
-  return out;
+  return crc_launch(vec ? pack_fp8_kernel<true> : pack_fp8_kernel<false>, src,
+                    dst.data_ptr<uint8_t>());
 }
 
 torch::Tensor pack_fp8_hash64_async(torch::Tensor src, torch::Tensor dst) {
-  TORCH_CHECK(src.is_cuda() && src.dtype() == torch::kBFloat16 &&
-                  src.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(src, torch::kBFloat16),
               "pack_fp8_hash64 expects contiguous CUDA bf16 src");
-  TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kUInt8 &&
-                  dst.is_contiguous() && dst.numel() >= src.numel(),
+  TORCH_CHECK(cuda_contiguous(dst, torch::kUInt8) &&
+                  dst.numel() >= src.numel(),
               "pack_fp8_hash64 dst too small");
   const unsigned long long n = src.numel();  // fp8 output bytes
-  auto out = torch::zeros(
-      {1}, torch::dtype(torch::kInt64).device(src.device()));
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(src.data_ptr()) & 15u) == 0 &&
-                  (reinterpret_cast<uintptr_t>(dst.data_ptr()) & 7u) == 0,
+  TORCH_CHECK(aligned_to(src.data_ptr(), 16) && aligned_to(dst.data_ptr(), 8),
               "pack_fp8_hash64 alignment");
-  const unsigned long long n_words = n / 8;
-  const uint32_t tail = (uint32_t)(n % 8);
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(pack_fp8_hash64_kernel, dim3(kHashLanes / kBlock),
-                     dim3(kBlock), 0, stream,
-                     reinterpret_cast<const uint16_t*>(src.data_ptr()),
-                     reinterpret_cast<unsigned long long*>(
-                         dst.data_ptr<uint8_t>()),
-                     n_words, tail, n,
-                     reinterpret_cast<unsigned long long*>(
-                         out.data_ptr<int64_t>()));
-  return out;
+  return hash64_launch(
+      src.device(), n,
+      [&](dim3 grid, hipStream_t stream, unsigned long long n_words,
+          uint32_t tail, unsigned long long* out) {
+        hipLaunchKernelGGL(pack_fp8_hash64_kernel, grid, dim3(kBlock), 0,
+                           stream, elem_ptr<const uint16_t>(src),
+                           elem_ptr<unsigned long long>(dst), n_words, tail, n,
+                           out);
+      });
 }
 
 torch::Tensor unpack_fp8_hash64_async(torch::Tensor src, torch::Tensor dst) {
-  TORCH_CHECK(src.is_cuda() && src.dtype() == torch::kUInt8 &&
-                  src.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(src, torch::kUInt8),
               "unpack_fp8_hash64 expects contiguous CUDA uint8 src");
-  TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kBFloat16 &&
-                  dst.is_contiguous() && dst.numel() == src.numel(),
+  TORCH_CHECK(cuda_contiguous(dst, torch::kBFloat16) &&
+                  dst.numel() == src.numel(),
               "unpack_fp8_hash64 dst mismatch");
   const unsigned long long n = src.numel();
-  auto out = torch::zeros(
-      {1}, torch::dtype(torch::kInt64).device(src.device()));
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(src.data_ptr()) & 7u) == 0 &&
-                  (reinterpret_cast<uintptr_t>(dst.data_ptr()) & 15u) == 0,
+  TORCH_CHECK(aligned_to(src.data_ptr(), 8) && aligned_to(dst.data_ptr(), 16),
               "unpack_fp8_hash64 alignment");
-  const unsigned long long n_words = n / 8;
-  const uint32_t tail = (uint32_t)(n % 8);
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(unpack_fp8_hash64_kernel, dim3(kHashLanes / kBlock),
-                     dim3(kBlock), 0, stream,
-                     reinterpret_cast<const unsigned long long*>(
-                         src.data_ptr<uint8_t>()),
-                     reinterpret_cast<uint16_t*>(dst.data_ptr()), n_words,
-                     tail, n,
-                     reinterpret_cast<unsigned long long*>(
-                         out.data_ptr<int64_t>()));
-  return out;
+  return hash64_launch(
+      src.device(), n,
+      [&](dim3 grid, hipStream_t stream, unsigned long long n_words,
+          uint32_t tail, unsigned long long* out) {
+        hipLaunchKernelGGL(unpack_fp8_hash64_kernel, grid, dim3(kBlock), 0,
+                           stream, elem_ptr<const unsigned long long>(src),
+                           elem_ptr<uint16_t>(dst), n_words, tail, n, out);
+      });
 }
 
 void unpack_fp8_async(torch::Tensor src, torch::Tensor dst) {
-  TORCH_CHECK(src.is_cuda() && src.dtype() == torch::kUInt8 &&
-                  src.is_contiguous(),
+  TORCH_CHECK(cuda_contiguous(src, torch::kUInt8),
               "unpack_fp8 expects contiguous CUDA uint8 src");
-  TORCH_CHECK(dst.is_cuda() && dst.dtype() == torch::kBFloat16 &&
-                  dst.is_contiguous() && dst.numel() == src.numel(),
+  TORCH_CHECK(cuda_contiguous(dst, torch::kBFloat16) &&
+                  dst.numel() == src.numel(),
               "unpack_fp8 dst mismatch");
   const unsigned long long n = src.numel();
   if (n == 0) return;
@@ -1070,45 +1063,57 @@ void unpack_fp8_async(torch::Tensor src, torch::Tensor dst) {
       aligned_to(src.data_ptr(), 8) && aligned_to(dst.data_ptr(), 16);
   hipLaunchKernelGGL(vec ? unpack_fp8_kernel<true> : unpack_fp8_kernel<false>,
                      dim3(blocks), dim3(kBlock), 0, stream,
-                     src.data_ptr<uint8_t>(),
-                     reinterpret_cast<uint16_t*>(dst.data_ptr()), n);
+                     src.data_ptr<uint8_t>(), elem_ptr<uint16_t>(dst), n);
 }
 
 torch::Tensor fedavg_combine_hash_async(torch::Tensor out,
                                         torch::Tensor local,
                                         torch::Tensor peer_bytes, double wa,
                                         double wb) {
-  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
-                  out.dtype() == torch::kBFloat16,
+  TORCH_CHECK(cuda_contiguous(out, torch::kBFloat16),
               "combine_hash: out must be contiguous CUDA bf16");
-  TORCH_CHECK(local.is_cuda() && local.is_contiguous() &&
-                  local.dtype() == torch::kBFloat16 &&
+  TORCH_CHECK(cuda_contiguous(local, torch::kBFloat16) &&
                   local.numel() == out.numel(),
               "combine_hash: local mismatch");
-  TORCH_CHECK(peer_bytes.is_cuda() && peer_bytes.is_contiguous() &&
-                  peer_bytes.dtype() == torch::kUInt8 &&
+  TORCH_CHECK(cuda_contiguous(peer_bytes, torch::kUInt8) &&
                   peer_bytes.numel() == out.numel() * 2,
               "combine_hash: peer byte count mismatch");
   const unsigned long long nbytes = peer_bytes.numel();
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(peer_bytes.data_ptr()) & 7u) == 0 &&
-                  (reinterpret_cast<uintptr_t>(local.data_ptr()) & 7u) == 0 &&
-                  (reinterpret_cast<uintptr_t>(out.data_ptr()) & 7u) == 0,
+  const uint8_t* p = peer_bytes.data_ptr<uint8_t>();
+  TORCH_CHECK(aligned_to(p, 8) && aligned_to(local.data_ptr(), 8) &&
+                  aligned_to(out.data_ptr(), 8),
               "combine_hash requires 8-byte alignment");
-  auto hash_out = torch::zeros(
-      {1}, torch::dtype(torch::kInt64).device(out.device()));
-  const unsigned long long n_words = nbytes / 8;
-  const uint32_t tail_len = (uint32_t)(nbytes % 8);
-  auto stream = at::hip::getCurrentHIPStream();
-  const uint8_t* p = static_cast<const uint8_t*>(peer_bytes.data_ptr());
-  hipLaunchKernelGGL(fedavg_combine_hash_kernel, dim3(kHashLanes / kBlock),
-                     dim3(kBlock), 0, stream,
-                     reinterpret_cast<uint16_t*>(out.data_ptr()),
-                     reinterpret_cast<const uint16_t*>(local.data_ptr()),
-                     reinterpret_cast<const unsigned long long*>(p), n_words,
-                     p + n_words * 8, tail_len, nbytes, (float)wa, (float)wb,
-                     reinterpret_cast<unsigned long long*>(
-                         hash_out.data_ptr<int64_t>()));
-  return hash_out;
+  return hash64_launch(
+      out.device(), nbytes,
+      [&](dim3 grid, hipStream_t stream, unsigned long long n_words,
+          uint32_t tail_len, unsigned long long* hash_out) {
+        hipLaunchKernelGGL(fedavg_combine_hash_kernel, grid, dim3(kBlock), 0,
+                           stream, elem_ptr<uint16_t>(out),
+                           elem_ptr<const uint16_t>(local),
+                           reinterpret_cast<const unsigned long long*>(p),
+                           n_words, p + n_words * 8, tail_len, nbytes,
+                           (float)wa, (float)wb, hash_out);
+      });
+}
+
+// Checks `inputs` against `out` and fills the kernel's table with the first
+// kMaxInputs of them (the callers bound the count, each in its own words).
+// Returns whether `out` and every input are 16-byte aligned.
+bool fill_reduce_args(ReduceArgs& args, const torch::Tensor& out,
+                      const std::vector<torch::Tensor>& inputs,
+                      const std::vector<double>& weights) {
+  const long long n = out.numel();
+  args.k = (int)inputs.size();
+  bool vec = aligned_to(out.data_ptr(), 16);
+  for (int j = 0; j < args.k && j < kMaxInputs; ++j) {
+    TORCH_CHECK(inputs[j].is_cuda() && inputs[j].is_contiguous() &&
+                    inputs[j].numel() == n && inputs[j].dtype() == out.dtype(),
+                "input ", j, " mismatch");
+    args.in[j] = inputs[j].data_ptr();
+    args.w[j] = (float)weights[j];
+    vec = vec && aligned_to(args.in[j], 16);
+  }
+  return vec;
 }
 
 void fedavg_reduce_(torch::Tensor out, std::vector<torch::Tensor> inputs,
@@ -1119,42 +1124,21 @@ void fedavg_reduce_(torch::Tensor out, std::vector<torch::Tensor> inputs,
   TORCH_CHECK(out.is_cuda() && out.is_contiguous(), "out must be CUDA contiguous");
   const unsigned long long n = out.numel();
   ReduceArgs args;
-  args.k = (int)inputs.size();
   // The kernel's uint4 accesses need every pointer 16-byte aligned; slices
   // of a flat buffer at odd element offsets take the scalar instantiation.
-  bool vec = aligned_to(out.data_ptr(), 16);
-  for (int j = 0; j < args.k; ++j) {
-    TORCH_CHECK(inputs[j].is_cuda() && inputs[j].is_contiguous() &&
-                    inputs[j].numel() == (long long)n &&
-                    inputs[j].dtype() == out.dtype(),
-                "input ", j, " mismatch");
-    args.in[j] = inputs[j].data_ptr();
-    args.w[j] = (float)weights[j];
-    vec = vec && aligned_to(args.in[j], 16);
-  }
+  const bool vec = fill_reduce_args(args, out, inputs, weights);
   auto stream = at::hip::getCurrentHIPStream();
   // >= 2048 workgroups to fill 256 CUs across 8 XCDs (guide §1).
   const int blocks = 4096;
-  if (out.dtype() == torch::kBFloat16) {
-    hipLaunchKernelGGL((vec ? fedavg_reduce_kernel<uint16_t, 8, true>
-                            : fedavg_reduce_kernel<uint16_t, 8, false>),
-                       dim3(blocks),
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<uint16_t*>(out.data_ptr()), args, n);
-  } else if (out.dtype() == torch::kHalf) {
-    hipLaunchKernelGGL((vec ? fedavg_reduce_kernel<__half, 8, true>
-                            : fedavg_reduce_kernel<__half, 8, false>),
-                       dim3(blocks),
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<__half*>(out.data_ptr()), args, n);
-  } else if (out.dtype() == torch::kFloat) {
-    hipLaunchKernelGGL((vec ? fedavg_reduce_kernel<float, 4, true>
-                            : fedavg_reduce_kernel<float, 4, false>),
-                       dim3(blocks),
-                       dim3(kBlock), 0, stream, out.data_ptr<float>(), args, n);
-  } else {
-    TORCH_CHECK(false, "fedavg_reduce_: unsupported dtype ", out.dtype());
-  }
+  dispatch_elem<kAnyFloat>(
+      out, "fedavg_reduce_: unsupported dtype ", [&](auto tag) {
+        using T = decltype(tag);
+        constexpr int VEC = 16 / (int)sizeof(T);  // one 16-byte load per lane
+        hipLaunchKernelGGL((vec ? fedavg_reduce_kernel<T, VEC, true>
+                                : fedavg_reduce_kernel<T, VEC, false>),
+                           dim3(blocks), dim3(kBlock), 0, stream,
+                           elem_ptr<T>(out), args, n);
+      });
 }
 
 void fedavg_reduce_mfma_(torch::Tensor out, std::vector<torch::Tensor> inputs,
@@ -1162,26 +1146,16 @@ void fedavg_reduce_mfma_(torch::Tensor out, std::vector<torch::Tensor> inputs,
   TORCH_CHECK(!inputs.empty() && inputs.size() <= 32,
               "fedavg_reduce_mfma_: 1..32 inputs");
   TORCH_CHECK(weights.size() == inputs.size(), "weights/inputs mismatch");
-  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
-                  out.dtype() == torch::kBFloat16,
+  TORCH_CHECK(cuda_contiguous(out, torch::kBFloat16),
               "out must be contiguous CUDA bf16");
   const unsigned long long n = out.numel();
   ReduceArgs args;
-  args.k = (int)inputs.size();
-  for (int j = 0; j < args.k && j < kMaxInputs; ++j) {
-    TORCH_CHECK(inputs[j].is_cuda() && inputs[j].is_contiguous() &&
-                    inputs[j].numel() == (long long)n &&
-                    inputs[j].dtype() == out.dtype(),
-                "input ", j, " mismatch");
-    args.in[j] = inputs[j].data_ptr();
-    args.w[j] = (float)weights[j];
-  }
+  fill_reduce_args(args, out, inputs, weights);
   TORCH_CHECK(args.k <= kMaxInputs,
               "fedavg_reduce_mfma_: pointer table limited to ", kMaxInputs);
   auto stream = at::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(fedavg_reduce_mfma_kernel, dim3(4096), dim3(kBlock), 0,
-                     stream, reinterpret_cast<uint16_t*>(out.data_ptr()), args,
-                     n);
+                     stream, elem_ptr<uint16_t>(out), args, n);
 }
 
 void masked_add_(torch::Tensor dst, torch::Tensor src, torch::Tensor mask) {
@@ -1199,19 +1173,13 @@ void masked_add_(torch::Tensor dst, torch::Tensor src, torch::Tensor mask) {
   const unsigned long long n = dst.numel();
   auto stream = at::hip::getCurrentHIPStream();
   const int blocks = 4096;
-  if (dst.dtype() == torch::kBFloat16) {
-    hipLaunchKernelGGL((masked_add_kernel<uint16_t>), dim3(blocks),
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<uint16_t*>(dst.data_ptr()),
-                       reinterpret_cast<const uint16_t*>(src.data_ptr()),
-                       static_cast<const uint8_t*>(mask.data_ptr()), n);
-  } else if (dst.dtype() == torch::kFloat) {
-    hipLaunchKernelGGL((masked_add_kernel<float>), dim3(blocks), dim3(kBlock),
-                       0, stream, dst.data_ptr<float>(), src.data_ptr<float>(),
-                       static_cast<const uint8_t*>(mask.data_ptr()), n);
-  } else {
-    TORCH_CHECK(false, "masked_add_: unsupported dtype ", dst.dtype());
-  }
+  dispatch_elem<kBf16 | kF32>(
+      dst, "masked_add_: unsupported dtype ", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((masked_add_kernel<T>), dim3(blocks), dim3(kBlock),
+                           0, stream, elem_ptr<T>(dst), elem_ptr<const T>(src),
+                           static_cast<const uint8_t*>(mask.data_ptr()), n);
+      });
 }
 
 int64_t crc32_combine_py(int64_t crc1, int64_t crc2, int64_t len2) {

@@ -1,7 +1,8 @@
 // Secure aggregation kernels — pairwise ChaCha20 masks in the ring Z/2^32.
 //
 // Included from rayfed_hip.hip inside its anonymous namespace (uses kBlock,
-// kMaxInputs, to_f32/from_f32).  The bit-exact specification and the numpy
+// kMaxInputs, to_f32/from_f32 and the host helpers aligned_to,
+// cuda_contiguous, dispatch_elem).  The bit-exact specification and the numpy
 // oracle are in rayfed_amd/ops/secagg_ref.py; tests/test_secagg_gpu.py pins
 // every path here against it.
 //
@@ -455,6 +456,13 @@ inline void secagg_check_range(const char* who, unsigned long long n,
               who, ": offset + n exceeds 2^36 (ChaCha20 counter would wrap)");
 }
 
+// Eight little-endian key words from 32 key bytes.
+inline void secagg_unpack_key(uint32_t dst[8], const uint8_t* p) {
+  for (int w = 0; w < 8; ++w, p += 4)
+    dst[w] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) |
+             ((uint32_t)p[3] << 24);
+}
+
 // Fill `dst` from rows [lo, lo+cnt) of a CPU uint8[K,32] / int32[K] pair.
 inline void secagg_fill_keys(SecaggKeys& dst, const torch::Tensor& keys,
                              const torch::Tensor& signs, int64_t lo,
@@ -463,11 +471,7 @@ inline void secagg_fill_keys(SecaggKeys& dst, const torch::Tensor& keys,
   const uint8_t* kp = keys.data_ptr<uint8_t>() + lo * 32;
   const int32_t* sp = signs.data_ptr<int32_t>() + lo;
   for (int64_t j = 0; j < cnt; ++j) {
-    for (int w = 0; w < 8; ++w) {
-      const uint8_t* p = kp + j * 32 + w * 4;
-      dst.key[j][w] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) |
-                      ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-    }
+    secagg_unpack_key(dst.key[j], kp + j * 32);
     dst.sign[j] = sp[j];
   }
 }
@@ -487,8 +491,16 @@ inline void secagg_check_keys(const char* who, const torch::Tensor& keys,
     TORCH_CHECK(sp[j] == 1 || sp[j] == -1, who, ": signs must be +1 or -1");
 }
 
-inline bool secagg_aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+// Where a launch sits in the keystream: the round is the ChaCha20 nonce's
+// first two words, the element offset the first block counter.
+struct SecaggPos {
+  unsigned long long blk0;
+  uint32_t n0, n1;
+};
+
+inline SecaggPos secagg_pos(uint64_t round, int64_t offset) {
+  return {(unsigned long long)offset / 16ull,
+          (uint32_t)(round & 0xffffffffull), (uint32_t)(round >> 32)};
 }
 
 // Enough workgroups to fill 256 CUs; the kernels grid-stride beyond that.
@@ -498,76 +510,62 @@ inline int secagg_grid(unsigned long long items) {
       4096ull, std::max<unsigned long long>(1ull, want));
 }
 
+// What secagg_mask and secagg_mask_noise share before their own launch: the
+// checks of x, out, the peers' keys and the range, and every kernel argument
+// that follows from them.  n may be 0; the caller then launches nothing.
+struct SecaggMaskPlan {
+  SecaggKeys keys{};
+  unsigned long long n;
+  SecaggPos pos;
+  float weight, scale;
+  bool vec_ok;
+  int blocks;
+  int32_t* out;
+};
+
+inline SecaggMaskPlan secagg_mask_plan(const char* who, const torch::Tensor& x,
+                                       const torch::Tensor& out,
+                                       const torch::Tensor& keys,
+                                       const torch::Tensor& signs,
+                                       uint64_t round, int64_t offset,
+                                       double weight, int64_t frac_bits) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), who,
+              ": x must be CUDA contiguous");
+  TORCH_CHECK(cuda_contiguous(out, torch::kInt32) &&
+                  out.numel() == x.numel() && out.device() == x.device(),
+              who,
+              ": out must be a contiguous int32 tensor of x's length on x's "
+              "device");
+  secagg_check_keys(who, keys, signs);
+  TORCH_CHECK(keys.size(0) <= kSecaggMaxKeys - 1, who, ": at most 15 peers");
+  SecaggMaskPlan p;
+  p.n = x.numel();
+  secagg_check_range(who, p.n, offset, frac_bits);
+  secagg_fill_keys(p.keys, keys, signs, 0, keys.size(0));
+  p.pos = secagg_pos(round, offset);
+  p.weight = (float)weight;
+  p.scale = (float)(1ull << frac_bits);
+  p.vec_ok = aligned_to(x.data_ptr(), 16) && aligned_to(out.data_ptr(), 16);
+  p.blocks = secagg_grid((p.n + 15ull) / 16ull);
+  p.out = out.data_ptr<int32_t>();
+  return p;
+}
+
 void secagg_mask_async(torch::Tensor x, torch::Tensor out, torch::Tensor keys,
                        torch::Tensor signs, uint64_t round, int64_t offset,
                        double weight, int64_t frac_bits) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
-              "secagg_mask: x must be CUDA contiguous");
-  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
-                  out.dtype() == torch::kInt32 &&
-                  out.numel() == x.numel() && out.device() == x.device(),
-              "secagg_mask: out must be a contiguous int32 tensor of x's "
-              "length on x's device");
-  secagg_check_keys("secagg_mask", keys, signs);
-  TORCH_CHECK(keys.size(0) <= kSecaggMaxKeys - 1,
-              "secagg_mask: at most 15 peers");
-  const unsigned long long n = x.numel();
-  secagg_check_range("secagg_mask", n, offset, frac_bits);
-  if (n == 0) return;
-  SecaggKeys k{};
-  secagg_fill_keys(k, keys, signs, 0, keys.size(0));
-  const bool vec_ok =
-      secagg_aligned16(x.data_ptr()) && secagg_aligned16(out.data_ptr());
-  const unsigned long long blk0 = (unsigned long long)offset / 16ull;
-  const uint32_t n0 = (uint32_t)(round & 0xffffffffull);
-  const uint32_t n1 = (uint32_t)(round >> 32);
-  const float w = (float)weight;
-  const float scale = (float)(1ull << frac_bits);
-  const int blocks = secagg_grid((n + 15ull) / 16ull);
+  const SecaggMaskPlan p = secagg_mask_plan("secagg_mask", x, out, keys, signs,
+                                            round, offset, weight, frac_bits);
+  if (p.n == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
-  int32_t* o = out.data_ptr<int32_t>();
-  if (x.dtype() == torch::kBFloat16) {
-    hipLaunchKernelGGL((secagg_mask_kernel<uint16_t>), dim3(blocks),
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<const uint16_t*>(x.data_ptr()), o, n,
-                       blk0, n0, n1, w, scale, k, vec_ok);
-  } else if (x.dtype() == torch::kHalf) {
-    hipLaunchKernelGGL((secagg_mask_kernel<__half>), dim3(blocks),
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<const __half*>(x.data_ptr()), o, n,
-                       blk0, n0, n1, w, scale, k, vec_ok);
-  } else if (x.dtype() == torch::kFloat) {
-    hipLaunchKernelGGL((secagg_mask_kernel<float>), dim3(blocks), dim3(kBlock),
-                       0, stream, x.data_ptr<float>(), o, n, blk0, n0, n1, w,
-                       scale, k, vec_ok);
-  } else {
-    TORCH_CHECK(false, "secagg_mask: unsupported dtype ", x.dtype());
-  }
-}
-
-template <typename T>
-void secagg_launch_mask_noise(int words, int blocks, hipStream_t stream,
-                              const T* x, int32_t* out, unsigned long long n,
-                              unsigned long long blk0, uint32_t n0,
-                              uint32_t n1, float w, float scale,
-                              const SecaggKeys& k, const SecaggNoiseKey& nk,
-                              uint32_t step, bool vec_ok) {
-#define SECAGG_NOISE_CASE(W)                                                 \
-  case W:                                                                    \
-    hipLaunchKernelGGL((secagg_mask_noise_kernel<T, W>), dim3(blocks),       \
-                       dim3(kBlock), 0, stream, x, out, n, blk0, n0, n1, w,  \
-                       scale, k, nk, step, vec_ok);                          \
-    break;
-  switch (words) {
-    SECAGG_NOISE_CASE(1)
-    SECAGG_NOISE_CASE(2)
-    SECAGG_NOISE_CASE(4)
-    SECAGG_NOISE_CASE(8)
-    SECAGG_NOISE_CASE(16)
-    default:
-      TORCH_CHECK(false, "secagg_mask_noise: words must be 1, 2, 4, 8 or 16");
-  }
-#undef SECAGG_NOISE_CASE
+  dispatch_elem<kAnyFloat>(
+      x, "secagg_mask: unsupported dtype ", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((secagg_mask_kernel<T>), dim3(p.blocks),
+                           dim3(kBlock), 0, stream, elem_ptr<const T>(x),
+                           p.out, p.n, p.pos.blk0, p.pos.n0, p.pos.n1,
+                           p.weight, p.scale, p.keys, p.vec_ok);
+      });
 }
 
 // max_blocks = 0: the normal grid; > 0 caps it (drives the grid-stride loop
@@ -578,19 +576,11 @@ void secagg_mask_noise_async(torch::Tensor x, torch::Tensor out,
                              int64_t step, uint64_t round, int64_t offset,
                              double weight, int64_t frac_bits,
                              int64_t max_blocks) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
-              "secagg_mask_noise: x must be CUDA contiguous");
-  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
-                  out.dtype() == torch::kInt32 &&
-                  out.numel() == x.numel() && out.device() == x.device(),
-              "secagg_mask_noise: out must be a contiguous int32 tensor of "
-              "x's length on x's device");
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 || x.dtype() == torch::kHalf ||
-                  x.dtype() == torch::kFloat,
-              "secagg_mask_noise: unsupported dtype ", x.dtype());
-  secagg_check_keys("secagg_mask_noise", keys, signs);
-  TORCH_CHECK(keys.size(0) <= kSecaggMaxKeys - 1,
-              "secagg_mask_noise: at most 15 peers");
+  const char* bad_dtype = "secagg_mask_noise: unsupported dtype ";
+  const SecaggMaskPlan p =
+      secagg_mask_plan("secagg_mask_noise", x, out, keys, signs, round, offset,
+                       weight, frac_bits);
+  TORCH_CHECK(elem_bit(x) & kAnyFloat, bad_dtype, x.dtype());
   TORCH_CHECK(!noise_key.is_cuda() && noise_key.dtype() == torch::kUInt8 &&
                   noise_key.is_contiguous() && noise_key.dim() == 1 &&
                   noise_key.size(0) == 32,
@@ -602,72 +592,46 @@ void secagg_mask_noise_async(torch::Tensor x, torch::Tensor out,
   TORCH_CHECK(step >= 1 && step <= kSecaggMaxNoiseStep,
               "secagg_mask_noise: step must be in [1, 2^20]");
   TORCH_CHECK(max_blocks >= 0, "secagg_mask_noise: max_blocks must be >= 0");
-  const unsigned long long n = x.numel();
-  secagg_check_range("secagg_mask_noise", n, offset, frac_bits);
   // offset + n <= 2^36 holds, so the product below cannot overflow 64 bits.
-  TORCH_CHECK(((unsigned long long)offset + n) * (unsigned long long)words <=
+  TORCH_CHECK(((unsigned long long)offset + p.n) * (unsigned long long)words <=
                   kSecaggMaxElements,
               "secagg_mask_noise: (offset + n) * words exceeds 2^36 (the "
               "noise stream's ChaCha20 counter would wrap)");
-  if (n == 0) return;
-  SecaggKeys k{};
-  secagg_fill_keys(k, keys, signs, 0, keys.size(0));
+  if (p.n == 0) return;
   SecaggNoiseKey nk{};
-  const uint8_t* np = noise_key.data_ptr<uint8_t>();
-  for (int w = 0; w < 8; ++w) {
-    const uint8_t* p = np + w * 4;
-    nk.key[w] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) |
-                ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-  }
-  const bool vec_ok =
-      secagg_aligned16(x.data_ptr()) && secagg_aligned16(out.data_ptr());
-  const unsigned long long blk0 = (unsigned long long)offset / 16ull;
-  const uint32_t n0 = (uint32_t)(round & 0xffffffffull);
-  const uint32_t n1 = (uint32_t)(round >> 32);
-  const float w = (float)weight;
-  const float scale = (float)(1ull << frac_bits);
-  int blocks = secagg_grid((n + 15ull) / 16ull);
-  if (max_blocks > 0 && max_blocks < blocks) blocks = (int)max_blocks;
+  secagg_unpack_key(nk.key, noise_key.data_ptr<uint8_t>());
+  const int blocks = (max_blocks > 0 && max_blocks < p.blocks)
+                         ? (int)max_blocks
+                         : p.blocks;
   auto stream = at::hip::getCurrentHIPStream();
-  int32_t* o = out.data_ptr<int32_t>();
-  if (x.dtype() == torch::kBFloat16) {
-    secagg_launch_mask_noise<uint16_t>(
-        (int)words, blocks, stream,
-        reinterpret_cast<const uint16_t*>(x.data_ptr()), o, n, blk0, n0, n1,
-        w, scale, k, nk, (uint32_t)step, vec_ok);
-  } else if (x.dtype() == torch::kHalf) {
-    secagg_launch_mask_noise<__half>(
-        (int)words, blocks, stream,
-        reinterpret_cast<const __half*>(x.data_ptr()), o, n, blk0, n0, n1, w,
-        scale, k, nk, (uint32_t)step, vec_ok);
-  } else {
-    secagg_launch_mask_noise<float>((int)words, blocks, stream,
-                                    x.data_ptr<float>(), o, n, blk0, n0, n1,
-                                    w, scale, k, nk, (uint32_t)step, vec_ok);
-  }
+  dispatch_elem<kAnyFloat>(x, bad_dtype, [&](auto tag) {
+    using T = decltype(tag);
+#define SECAGG_NOISE_CASE(W)                                                  \
+  case W:                                                                     \
+    hipLaunchKernelGGL((secagg_mask_noise_kernel<T, W>), dim3(blocks),        \
+                       dim3(kBlock), 0, stream, elem_ptr<const T>(x), p.out,  \
+                       p.n, p.pos.blk0, p.pos.n0, p.pos.n1, p.weight,         \
+                       p.scale, p.keys, nk, (uint32_t)step, p.vec_ok);        \
+    break;
+    switch (words) {
+      SECAGG_NOISE_CASE(1)
+      SECAGG_NOISE_CASE(2)
+      SECAGG_NOISE_CASE(4)
+      SECAGG_NOISE_CASE(8)
+      SECAGG_NOISE_CASE(16)
+    }
+#undef SECAGG_NOISE_CASE
+  });
 }
 
 // Enough blocks for 8 waves per SIMD on 256 CUs; one double per block.
 constexpr int kSumsqMaxBlocks = 2048;
 
-template <typename T>
-void sumsq_launch(const T* x, unsigned long long n, int blocks,
-                  double* partials, hipStream_t stream) {
-  if (secagg_aligned16(x)) {
-    hipLaunchKernelGGL((sumsq_kernel<T, true>), dim3(blocks), dim3(kBlock), 0,
-                       stream, x, n, partials);
-  } else {
-    hipLaunchKernelGGL((sumsq_kernel<T, false>), dim3(blocks), dim3(kBlock),
-                       0, stream, x, n, partials);
-  }
-}
-
 torch::Tensor sumsq_async(torch::Tensor x) {
+  const char* bad_dtype = "sumsq: unsupported dtype ";
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
               "sumsq: x must be CUDA contiguous");
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 || x.dtype() == torch::kHalf ||
-                  x.dtype() == torch::kFloat,
-              "sumsq: unsupported dtype ", x.dtype());
+  TORCH_CHECK(elem_bit(x) & kAnyFloat, bad_dtype, x.dtype());
   auto opts = torch::dtype(torch::kFloat64).device(x.device());
   const unsigned long long n = x.numel();
   if (n == 0) return torch::zeros({1}, opts);
@@ -680,15 +644,13 @@ torch::Tensor sumsq_async(torch::Tensor x) {
   auto partials = torch::empty({(long long)blocks}, opts);
   auto stream = at::hip::getCurrentHIPStream();
   double* pp = partials.data_ptr<double>();
-  if (x.dtype() == torch::kBFloat16) {
-    sumsq_launch<uint16_t>(reinterpret_cast<const uint16_t*>(x.data_ptr()), n,
-                           blocks, pp, stream);
-  } else if (x.dtype() == torch::kHalf) {
-    sumsq_launch<__half>(reinterpret_cast<const __half*>(x.data_ptr()), n,
-                         blocks, pp, stream);
-  } else {
-    sumsq_launch<float>(x.data_ptr<float>(), n, blocks, pp, stream);
-  }
+  const bool vec = aligned_to(x.data_ptr(), 16);
+  dispatch_elem<kAnyFloat>(x, bad_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(
+        (vec ? sumsq_kernel<T, true> : sumsq_kernel<T, false>), dim3(blocks),
+        dim3(kBlock), 0, stream, elem_ptr<const T>(x), n, pp);
+  });
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(kBlock), 0, stream,
                      static_cast<const double*>(pp), blocks,
                      out.data_ptr<double>());
@@ -697,29 +659,13 @@ torch::Tensor sumsq_async(torch::Tensor x) {
 
 template <typename OutT, int EPL>
 void secagg_launch_aggregate(OutT* out, const SecaggInputs& ins,
-                             unsigned long long n, unsigned long long blk0,
-                             uint32_t n0, uint32_t n1, float inv_scale,
-                             const SecaggKeys& corr, bool vec_ok,
-                             hipStream_t stream) {
+                             unsigned long long n, const SecaggPos& pos,
+                             float inv_scale, const SecaggKeys& corr,
+                             bool vec_ok, hipStream_t stream) {
   const int blocks = secagg_grid((n + EPL - 1ull) / EPL);
   hipLaunchKernelGGL((secagg_aggregate_kernel<OutT, EPL>), dim3(blocks),
-                     dim3(kBlock), 0, stream, out, ins, n, blk0, n0, n1,
-                     inv_scale, corr, vec_ok);
-}
-
-template <typename OutT>
-void secagg_launch_final(OutT* out, const SecaggInputs& ins,
-                         unsigned long long n, unsigned long long blk0,
-                         uint32_t n0, uint32_t n1, float inv_scale,
-                         const SecaggKeys& corr, bool vec_ok,
-                         hipStream_t stream) {
-  if (corr.k == 0) {
-    secagg_launch_aggregate<OutT, 4>(out, ins, n, blk0, n0, n1, inv_scale,
-                                     corr, vec_ok, stream);
-  } else {
-    secagg_launch_aggregate<OutT, 16>(out, ins, n, blk0, n0, n1, inv_scale,
-                                      corr, vec_ok, stream);
-  }
+                     dim3(kBlock), 0, stream, out, ins, n, pos.blk0, pos.n0,
+                     pos.n1, inv_scale, corr, vec_ok);
 }
 
 void secagg_aggregate_async(torch::Tensor out,
@@ -727,6 +673,7 @@ void secagg_aggregate_async(torch::Tensor out,
                             torch::Tensor corr_keys, torch::Tensor corr_signs,
                             uint64_t round, int64_t offset,
                             int64_t frac_bits) {
+  const char* bad_dtype = "secagg_aggregate: unsupported out dtype ";
   TORCH_CHECK(!inputs.empty() && inputs.size() <= kMaxInputs,
               "secagg_aggregate: 1..16 inputs");
   TORCH_CHECK(out.is_cuda() && out.is_contiguous(),
@@ -734,25 +681,20 @@ void secagg_aggregate_async(torch::Tensor out,
   secagg_check_keys("secagg_aggregate", corr_keys, corr_signs);
   const unsigned long long n = out.numel();
   secagg_check_range("secagg_aggregate", n, offset, frac_bits);
-  TORCH_CHECK(out.dtype() == torch::kFloat || out.dtype() == torch::kHalf ||
-                  out.dtype() == torch::kBFloat16,
-              "secagg_aggregate: unsupported out dtype ", out.dtype());
+  TORCH_CHECK(elem_bit(out) & kAnyFloat, bad_dtype, out.dtype());
   SecaggInputs ins;
   ins.k = (int)inputs.size();
-  bool vec_ok = secagg_aligned16(out.data_ptr());
+  bool vec_ok = aligned_to(out.data_ptr(), 16);
   for (int j = 0; j < ins.k; ++j) {
-    TORCH_CHECK(inputs[j].is_cuda() && inputs[j].is_contiguous() &&
+    TORCH_CHECK(cuda_contiguous(inputs[j], torch::kInt32) &&
                     inputs[j].numel() == (long long)n &&
-                    inputs[j].dtype() == torch::kInt32 &&
                     inputs[j].device() == out.device(),
                 "secagg_aggregate: input ", j, " mismatch");
     ins.in[j] = inputs[j].data_ptr<int32_t>();
-    vec_ok = vec_ok && secagg_aligned16(ins.in[j]);
+    vec_ok = vec_ok && aligned_to(ins.in[j], 16);
   }
   if (n == 0) return;
-  const unsigned long long blk0 = (unsigned long long)offset / 16ull;
-  const uint32_t n0 = (uint32_t)(round & 0xffffffffull);
-  const uint32_t n1 = (uint32_t)(round >> 32);
+  const SecaggPos pos = secagg_pos(round, offset);
   const float inv_scale = 1.0f / (float)(1ull << frac_bits);
   auto stream = at::hip::getCurrentHIPStream();
 
@@ -769,25 +711,23 @@ void secagg_aggregate_async(torch::Tensor out,
                          torch::dtype(torch::kInt32).device(out.device()));
     }
     secagg_launch_aggregate<int32_t, 16>(
-        acc.data_ptr<int32_t>(), ins, n, blk0, n0, n1, 0.0f, corr,
-        vec_ok && secagg_aligned16(acc.data_ptr()), stream);
+        acc.data_ptr<int32_t>(), ins, n, pos, 0.0f, corr,
+        vec_ok && aligned_to(acc.data_ptr(), 16), stream);
     ins.k = 1;
     ins.in[0] = acc.data_ptr<int32_t>();
-    vec_ok = secagg_aligned16(out.data_ptr()) &&
-             secagg_aligned16(acc.data_ptr());
+    vec_ok = aligned_to(out.data_ptr(), 16) && aligned_to(acc.data_ptr(), 16);
     done += kSecaggMaxKeys;
   }
   secagg_fill_keys(corr, corr_keys, corr_signs, done, C - done);
-  if (out.dtype() == torch::kBFloat16) {
-    secagg_launch_final<uint16_t>(reinterpret_cast<uint16_t*>(out.data_ptr()),
-                                  ins, n, blk0, n0, n1, inv_scale, corr,
-                                  vec_ok, stream);
-  } else if (out.dtype() == torch::kHalf) {
-    secagg_launch_final<__half>(reinterpret_cast<__half*>(out.data_ptr()), ins,
-                                n, blk0, n0, n1, inv_scale, corr, vec_ok,
-                                stream);
-  } else {
-    secagg_launch_final<float>(out.data_ptr<float>(), ins, n, blk0, n0, n1,
-                               inv_scale, corr, vec_ok, stream);
-  }
+  // Without corrections in the last launch it is the streaming reduce.
+  dispatch_elem<kAnyFloat>(out, bad_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (corr.k == 0) {
+      secagg_launch_aggregate<T, 4>(elem_ptr<T>(out), ins, n, pos, inv_scale,
+                                    corr, vec_ok, stream);
+    } else {
+      secagg_launch_aggregate<T, 16>(elem_ptr<T>(out), ins, n, pos, inv_scale,
+                                     corr, vec_ok, stream);
+    }
+  });
 }
